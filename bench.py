@@ -14,6 +14,13 @@ send/recv over xGMI, and the per-target mark words are all-gathered so that
 every rank replays the exact serial processed-mask. Total work is fixed, so
 scaling is "strong".
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric,
+value, ms_per_step, ...). --full adds what takes runs of its own: per-kernel
+times, the roofline, the CPU baseline and the parity / PSNR comparison with
+the CPU oracle, the first-frame and host-API times (--no-cpu / --no-extras
+drop parts of it). --dump-outputs DIR writes what the last timed step computed
+as DIR/<name>.npy (float32); the inputs are seeded, the same on every run.
 """
 import argparse
 import importlib
@@ -48,6 +55,24 @@ _JSON_FD = 1
 
 def emit(res):
     os.write(_JSON_FD, (json.dumps(res) + "\n").encode())
+
+
+DUMP_BYTES = 60 << 20    # --dump-outputs: at most this many bytes of arrays in all (< 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <path>/<name>.npy (float32) per array of {name: host array}. If they hold more than
+    DUMP_BYTES together, each is replaced by the same fixed, seeded sample of its flattened elements (its share of
+    the budget), so that two builds are compared element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > DUMP_BYTES:
+            n = a.size * DUMP_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(20240).choice(a.size, n, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E peak 8 TB/s
@@ -263,7 +288,20 @@ def bench_flow(args, pkg, synth, ctx, torch, dist, rank, world, dev):
         dt = float(tt.item())
     if rank != 0:
         return
+    if args.dump_outputs:      # (before the roofline's run below writes `flow` again)
+        dump_outputs(args.dump_outputs, {"flow": flow.cpu().numpy()})
     ms = dt / args.steps * 1e3
+    res = {"metric": "Mpix/s per flow (tvl1flow, 1080p, default parameters)", "value": round(world * w * h / (dt / args.steps) / 1e6, 3),
+           "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "clock_settle_steps": settle,
+           "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f32", "data": "synthetic",
+           "config": {"workload": f"F1: dual TV-L1 flow between two {w}x{h} noisy frames (sigma {sigma:g}), "
+                                  f"tau 0.25 lambda 0.15 theta 0.3, {prm.nscales} scales, 5 warps, epsilon 0.01",
+                      "parallelism": "single GPU" if world == 1 else f"{world} independent replicas",
+                      "iterations": iters}}
+    if not args.full:
+        emit(res)
+        return
     # roofline of the dominant kernel (k_tv_block at full size): a one-level run is nothing but
     # its iterations (+ 5 warps). Algorithmic bytes: an iteration reads 16 and writes 6 floats per
     # pixel = 88 B; the kernel runs 4 iterations per launch on LDS tiles, so its real
@@ -288,25 +326,17 @@ def bench_flow(args, pkg, synth, ctx, torch, dist, rank, world, dev):
     # HBM-side bytes per iteration from the committed PMC passes of the same sources (a launch = 4 iterations)
     traffic, traffic_note = (None, "single-GPU runs only") if world > 1 else measured_traffic("F1", "k_tv_block", largest_grid=True)
     traffic = traffic / 4 if traffic else None
-    res = {"metric": "Mpix/s per flow (tvl1flow, 1080p, default parameters)", "value": round(world * w * h / (dt / args.steps) / 1e6, 3),
-           "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "clock_settle_steps": settle,
-           "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "f32", "data": "synthetic",
-           "config": {"workload": f"F1: dual TV-L1 flow between two {w}x{h} noisy frames (sigma {sigma:g}), "
-                                  f"tau 0.25 lambda 0.15 theta 0.3, {prm.nscales} scales, 5 warps, epsilon 0.01",
-                      "parallelism": "single GPU" if world == 1 else f"{world} independent replicas",
-                      "iterations": iters},
-           "roofline": {"kernel": "k_tv_block (full-size level, per iteration)", "bound": "hbm",
-                        "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_note": traffic_note,
-                        "iteration_us": round(t_iter * 1e6, 2), "algorithmic_bytes_per_iteration": 22 * w * h,
-                        "traffic_frac": (round(traffic / t_iter / 1e9 / HBM_PEAK_GBS, 4) if traffic else None),
-                        "equivalent_unblocked_gbs": round(gbs_equiv, 1),
-                        "note": "measured on a one-level run (wall time / iterations; launches, redone "
-                                "batches and state read-backs included). achieved = the blocked kernel's "
-                                "compulsory bytes (88 B per pixel per 4-iteration launch) / time; traffic_frac = "
-                                "PMC-counted bytes / time / peak; equivalent_unblocked_gbs = what a one-launch-"
-                                "per-iteration recursion would have to move in the same time (not an HBM fraction)"}}
+    res["roofline"] = {"kernel": "k_tv_block (full-size level, per iteration)", "bound": "hbm",
+                       "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_note": traffic_note,
+                       "iteration_us": round(t_iter * 1e6, 2), "algorithmic_bytes_per_iteration": 22 * w * h,
+                       "traffic_frac": (round(traffic / t_iter / 1e9 / HBM_PEAK_GBS, 4) if traffic else None),
+                       "equivalent_unblocked_gbs": round(gbs_equiv, 1),
+                       "note": "measured on a one-level run (wall time / iterations; launches, redone "
+                               "batches and state read-backs included). achieved = the blocked kernel's "
+                               "compulsory bytes (88 B per pixel per 4-iteration launch) / time; traffic_frac = "
+                               "PMC-counted bytes / time / peak; equivalent_unblocked_gbs = what a one-launch-"
+                               "per-iteration recursion would have to move in the same time (not an HBM fraction)"}
     if not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as O
@@ -400,9 +430,10 @@ def bench_sequence(args, pkg, synth, ctx, torch, rank, world, dev):
     dt = (time.perf_counter() - t0) / ns  # time per frame of the aggregate = wall / (steps * ns)
     k += args.steps
     sf = sfs[0]
-    c1, n1 = cleans[(k - 1) % nfr], noisy[(k - 1) % nfr].cpu().numpy()
     ms = dt / args.steps * 1e3
-    out = sf.download_rgb(sf.flt2)
+    out = sf.download_rgb(sf.flt2) if args.full or args.dump_outputs else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"flt2_rgb": out})
     res = {"metric": "Mpix/s per frame (flow + mask + nlkalman-flt x2, 1080p sigma=20, frames resident)",
            "value": round(w * h / (dt / args.steps) / 1e6, 3), "unit": "Mpix/s", "n_gpus": 1,
            "steps": args.steps, "warmup": args.warmup, "clock_settle_steps": settle, "ms_per_step": round(ms, 4), "higher_is_better": True,
@@ -411,10 +442,12 @@ def bench_sequence(args, pkg, synth, ctx, torch, rank, world, dev):
                                   "to the previous FLT2 output, occlusion mask (0.75), warp + FLT1, warp + FLT2 "
                                   "(defaults of nlkalman_default_params), nothing leaves HBM",
                       "parallelism": "single GPU" if ns == 1 else f"single GPU, {ns} concurrent sequences",
-                      "flow_iterations_last_frame": sf.flow_iterations[-1]},
-           "psnr_flt2_db": round(float(synth.psnr(out, c1)), 4),
-           "psnr_noisy_db": round(float(synth.psnr(n1, c1)), 4)}
-    if ns == 1:
+                      "flow_iterations_last_frame": sf.flow_iterations[-1]}}
+    if args.full:
+        c1, n1 = cleans[(k - 1) % nfr], noisy[(k - 1) % nfr].cpu().numpy()
+        res["psnr_flt2_db"] = round(float(synth.psnr(out, c1)), 4)
+        res["psnr_noisy_db"] = round(float(synth.psnr(n1, c1)), 4)
+    if ns == 1 and args.full:
         # where a frame goes: a second, PROFILED pass of the same frames with a device sync after every stage
         # (not part of `value`; the syncs cost the stages their overlap with the host's enqueueing)
         nprof = min(args.steps, 20)
@@ -497,7 +530,7 @@ def launch_ranks(args):
 
     The run cannot end without a line because a step HANGS (the C strip driver's neighbour send / recv has never
     met a second device - DESIGN.md §6): the child runs under a time limit (NLK_BENCH_LAUNCH_TIMEOUT seconds;
-    default 300 + 120 for the CPU legs + 50 ms per step - a fresh box pages torch in for a minute or two); past
+    default 300 + 120 for the CPU legs of --full + 50 ms per step - a fresh box pages torch in for a minute or two); past
     it, its whole process group is killed and a FRESH child is started with the Python strip driver
     (--strip-driver py; never a process that has touched the GPU re-used or re-exec'ed), and the line says
     which driver produced it and why (`launch`)."""
@@ -508,7 +541,7 @@ def launch_ranks(args):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: what RCCL needs on this driver
     limit = float(os.environ.get("NLK_BENCH_LAUNCH_TIMEOUT",
-                                 300 + (0 if args.no_cpu else 120) + 0.05 * (args.steps + args.warmup)))
+                                 300 + (120 if args.full and not args.no_cpu else 0) + 0.05 * (args.steps + args.warmup)))
 
     def run_once(extra):
         with socket.socket() as sk:
@@ -652,7 +685,12 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="C2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: per-kernel times, roofline, CPU baseline, parity / PSNR against the "
+                         "CPU oracle, first-frame and host-API times (each in runs of its own; off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--streams", type=int, default=1,
                     help="workload S1: independent sequences run concurrently on the GPU (one context, "
                          "HIP stream and host thread each); value = aggregate")
@@ -666,7 +704,7 @@ def main():
                     help="row-strip runs: the step enqueued from C (csrc/strips.hip: RCCL called from C, one ctypes call "
                          "per step - the default) or from Python (strips.py over torch.distributed)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip first_frame_ms / api_wall_ms (profiler passes: only the timed call's kernels run)")
+                    help="--full: skip first_frame_ms / api_wall_ms (profiler passes: only the timed call's kernels run)")
     ap.add_argument("--strip-model", action="store_true",
                     help="N = 1 only: additionally step ONE middle rank of a world of 2 / 4 / 8 alone, every exchange "
                          "skipped (csrc/strips.hip dry run): the kernels + launch gaps one rank pays per frame at that "
@@ -676,6 +714,8 @@ def main():
     ap.add_argument("--strip-graph", action="store_true",
                     help="C strip driver: capture the step into a HIP graph once and replay it")
     args = ap.parse_args()
+    if args.preflight_child:
+        args.dump_outputs = None    # (the trial step of run_preflight is not the run)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: start the N ranks as CHILD processes before this
@@ -964,55 +1004,62 @@ def main():
         one_step()
     barrier()
     dt = time.perf_counter() - t0
-    # Per-kernel times: a second, untimed loop of the same steps with HIP events around every kernel
-    # on the context's stream (the timed loop above runs the same single-stream order, unprofiled).
+    striped = world > 1 or args.force_strips
+    dumped = None
+    if args.dump_outputs and rank == 0 and (args.workload == "C5" or not striped):
+        # (taken now: the loops of --full below run the step again; row strips: the frame assembled further down)
+        dumped = {"smoothed": t_out, "flt2": t_f2} if args.workload == "C5" else {"denoised": t_out}
+        dumped = {k_: v_.cpu().numpy() for k_, v_ in dumped.items()}
     if cs is not None:
         _, issue_us, replayed = cs.stats()          # (of the timed loop)
-        cs.set_options(overlap=False, timing=False, graph=False)   # (a replayed graph carries no profiling events)
-    ctx.set_profiling(True)
-    for _ in range(args.steps):
-        one_step()
-    barrier()
-    tm = ctx.timings()
-    c5 = None
-    if args.workload == "C5":
-        # the chain's three calls one at a time (HIP events around every kernel, as above): which launch dominates and
-        # what it did - the smoother's records feed its roofline below (missing 3 / next 2)
-        c5 = {}
-        for name_, call_ in (("flt1", lambda: ctx.filter_frame(t_f1.data_ptr(), t_n1.data_ptr(), t_prev.data_ptr(), None, w, h, ch, sigma, p)),
-                             ("flt2", lambda: ctx.filter_frame(t_f2.data_ptr(), t_n1.data_ptr(), t_prev.data_ptr(), t_f1.data_ptr(), w, h, ch, sigma, p2)),
-                             ("smo1", lambda: ctx.smooth_frame(t_out.data_ptr(), t_prev.data_ptr(), t_f2.data_ptr(), None, w, h, ch, sigma, ps))):
-            call_()
-            barrier()
-            ctx.set_profiling(False)
-            ctx.set_profiling(True)     # (restarts the sums)
-            for _ in range(args.steps):
+    tm, c5, ntr_local, nother_local = None, None, 0.0, 0.0
+    if args.full:
+        # Per-kernel times: a second, untimed loop of the same steps with HIP events around every kernel
+        # on the context's stream (the timed loop above runs the same single-stream order, unprofiled).
+        if cs is not None:
+            cs.set_options(overlap=False, timing=False, graph=False)   # (a replayed graph carries no profiling events)
+        ctx.set_profiling(True)
+        for _ in range(args.steps):
+            one_step()
+        barrier()
+        tm = ctx.timings()
+        if args.workload == "C5":
+            # the chain's three calls one at a time (HIP events around every kernel, as above): which launch dominates and
+            # what it did - the smoother's records feed its roofline below (missing 3 / next 2)
+            c5 = {}
+            for name_, call_ in (("flt1", lambda: ctx.filter_frame(t_f1.data_ptr(), t_n1.data_ptr(), t_prev.data_ptr(), None, w, h, ch, sigma, p)),
+                                 ("flt2", lambda: ctx.filter_frame(t_f2.data_ptr(), t_n1.data_ptr(), t_prev.data_ptr(), t_f1.data_ptr(), w, h, ch, sigma, p2)),
+                                 ("smo1", lambda: ctx.smooth_frame(t_out.data_ptr(), t_prev.data_ptr(), t_f2.data_ptr(), None, w, h, ch, sigma, ps))):
                 call_()
-            barrier()
-            c5[name_] = {"ms": ctx.timings(), "rec": ctx.read_records()}
-    ctx.set_profiling(False)
-    striped = world > 1 or args.force_strips
-    # transforms this rank's group kernel really ran (from its records): the roofline's flops
-    import numpy as np
-    rec = ctx.read_records()
-    if striped and args.workload != "C5" and cs is not None:
-        geo = cs.geometry(0)
-        _, _, _, act_ptr = cs.own_rows(0)
-        act = ctx.download(act_ptr, (ngx * ngy,), np.uint8)[geo["gy0"] * ngx:geo["gy1"] * ngx].astype(bool)
-    elif striped and args.workload != "C5":
-        p_ = sf.p
-        act = sf.active_full[p_["gy0"] * sf.ngx:p_["gy1"] * sf.ngx].cpu().numpy().astype(bool)
-    else:
-        act = rec["active"].astype(bool)
-    act = act & (rec["nagg"] > 0)
-    # ALGORITHMIC work of the group kernel (SURVEY.md §8(d) terms, per processed target): forward transforms of the
-    # kept candidates (image, and previous frame when the target has valid previous patches), inverse transforms of
-    # the group members (their forward transforms ARE candidate transforms: the kernels redo them, the algorithm
-    # does not), statistics 16 flop per coefficient and candidate, gains 68 per coefficient, aggregation 2 per
-    # member pixel and plane. Summed from the last launch's records.
-    nsel_a, np0_a, nagg_a = (rec[k_][act].astype(np.float64) for k_ in ("nsel", "np0", "nagg"))
-    ntr_local = float((nsel_a * (1 + (np0_a > 0)) + nagg_a).sum())                     # patch transforms per channel
-    nother_local = float((nsel_a * ch * psz * psz * 16 + ch * psz * psz * 68 + nagg_a * psz * psz * (ch + 1) * 2).sum())
+                barrier()
+                ctx.set_profiling(False)
+                ctx.set_profiling(True)     # (restarts the sums)
+                for _ in range(args.steps):
+                    call_()
+                barrier()
+                c5[name_] = {"ms": ctx.timings(), "rec": ctx.read_records()}
+        ctx.set_profiling(False)
+        # transforms this rank's group kernel really ran (from its records): the roofline's flops
+        import numpy as np
+        rec = ctx.read_records()
+        if striped and args.workload != "C5" and cs is not None:
+            geo = cs.geometry(0)
+            _, _, _, act_ptr = cs.own_rows(0)
+            act = ctx.download(act_ptr, (ngx * ngy,), np.uint8)[geo["gy0"] * ngx:geo["gy1"] * ngx].astype(bool)
+        elif striped and args.workload != "C5":
+            p_ = sf.p
+            act = sf.active_full[p_["gy0"] * sf.ngx:p_["gy1"] * sf.ngx].cpu().numpy().astype(bool)
+        else:
+            act = rec["active"].astype(bool)
+        act = act & (rec["nagg"] > 0)
+        # ALGORITHMIC work of the group kernel (SURVEY.md §8(d) terms, per processed target): forward transforms of the
+        # kept candidates (image, and previous frame when the target has valid previous patches), inverse transforms of
+        # the group members (their forward transforms ARE candidate transforms: the kernels redo them, the algorithm
+        # does not), statistics 16 flop per coefficient and candidate, gains 68 per coefficient, aggregation 2 per
+        # member pixel and plane. Summed from the last launch's records.
+        nsel_a, np0_a, nagg_a = (rec[k_][act].astype(np.float64) for k_ in ("nsel", "np0", "nagg"))
+        ntr_local = float((nsel_a * (1 + (np0_a > 0)) + nagg_a).sum())                     # patch transforms per channel
+        nother_local = float((nsel_a * ch * psz * psz * 16 + ch * psz * psz * 68 + nagg_a * psz * psz * (ch + 1) * 2).sum())
     phase_ms, strip_info = None, None
     if cs is not None:
         strip_info = {"driver": "C (csrc/strips.hip), one call per step", "transport": cs.transport(),
@@ -1036,10 +1083,11 @@ def main():
         sf.timers = False
         phase_ms = {k_: round(v / args.steps * 1e3, 4) for k_, v in sf.phase_s.items()}
     if world > 1:
-        tt = torch.tensor([dt, tm["group_ms"], tm["match_ms"]], dtype=torch.float64, device=dev)
+        tt = torch.tensor([dt] + ([tm["group_ms"], tm["match_ms"]] if tm is not None else []), dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt[0].item())
-        tm["group_ms"], tm["match_ms"] = float(tt[1].item()), float(tt[2].item())   # slowest rank
+        if tm is not None:
+            tm["group_ms"], tm["match_ms"] = float(tt[1].item()), float(tt[2].item())   # slowest rank
         ts = torch.tensor([ntr_local, nother_local], dtype=torch.float64, device=dev)
         dist.all_reduce(ts)
         ntr_total, nother_total = float(ts[0].item()), float(ts[1].item())
@@ -1063,10 +1111,34 @@ def main():
             y0, y1, rows_ptr, _ = cs.own_rows(0)
             ctx.d2d(t_out.data_ptr(), rows_ptr, (y1 - y0) * w * ch * 4)
             ctx.sync()
+        elif striped and args.workload != "C5":
+            y0, y1, rows = sf.own_rows()
+            t_out[y0:y1] = rows
 
     if rank == 0:
         ms = dt / args.steps * 1e3
         value = w * h / (dt / args.steps) / 1e6
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dumped if dumped is not None else {"denoised": t_out.cpu().numpy()})
+        res = {"metric": "Mpix/s per frame (nlkalman-flt, 1080p sigma=20)"
+               if args.workload == "C2" else f"Mpix/s per frame (nlkalman-flt, {args.workload})",
+               "value": round(value, 3), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps,
+               "warmup": args.warmup, "clock_settle_steps": settle,
+               "ms_per_step_first_20_unsettled": round(ramp_ms, 4) if ramp_ms is not None else None,
+               "ms_per_step": round(ms, 4), "higher_is_better": True,
+               "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+               "config": {"workload": f"{args.workload}: {w}x{h}x{ch} synthetic AWGN sigma={sigma:g}, "
+                                      f"FLT1 temporal (deno0 = spatial FLT1 of frame 0, bsic1=NULL), "
+                                      f"patch {psz}, defaults of nlkalman_default_params",
+                          "parallelism": f"row strips x{world}" if world > 1 else "single GPU",
+                          "mask_order": "serial-exact" if world == 1 else
+                          "serial-exact (mark words all-gathered, mask replayed on every rank)",
+                          # (the opt-in block-summed distance order, 8 x 8 patches: k_match.h; `value` of a default run
+                          # is always the exact order)
+                          "match_order": ("block-summed (NLK_MATCH_ORDER=block: NOT the reference's summation order)"
+                                          if os.environ.get("NLK_MATCH_ORDER", "") in ("block", "1") and psz == 8
+                                          else "exact (the reference's hy, hx, c order)")}}
+    if rank == 0 and args.full:
         out = t_out.cpu().numpy()
         # dominant kernel and its roofline; algorithmic bytes and flops: DESIGN.md §5.
         # The group kernel runs its DCTs on the f32 matrix cores and everything else on the
@@ -1122,31 +1194,13 @@ def main():
                         "~550 flop per algorithmic byte: compute bound. frac = transform flops only (matrix cores); "
                         "the vector-ALU share of the same launch is roofline.valu; f32 MFMA and f32 VALU share "
                         "the FP32 datapath on gfx950: see DESIGN.md §5"}
-        res = {"metric": "Mpix/s per frame (nlkalman-flt, 1080p sigma=20)"
-               if args.workload == "C2" else f"Mpix/s per frame (nlkalman-flt, {args.workload})",
-               "value": round(value, 3), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "clock_settle_steps": settle,
-               "ms_per_step_first_20_unsettled": round(ramp_ms, 4) if ramp_ms is not None else None,
-               "ms_per_step": round(ms, 4), "higher_is_better": True,
-               "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-               "config": {"workload": f"{args.workload}: {w}x{h}x{ch} synthetic AWGN sigma={sigma:g}, "
-                                      f"FLT1 temporal (deno0 = spatial FLT1 of frame 0, bsic1=NULL), "
-                                      f"patch {psz}, defaults of nlkalman_default_params",
-                          "parallelism": f"row strips x{world}" if world > 1 else "single GPU",
-                          "mask_order": "serial-exact" if world == 1 else
-                          "serial-exact (mark words all-gathered, mask replayed on every rank)",
-                          # (the opt-in block-summed distance order, 8 x 8 patches: k_match.h; `value` of a default run
-                          # is always the exact order)
-                          "match_order": ("block-summed (NLK_MATCH_ORDER=block: NOT the reference's summation order)"
-                                          if os.environ.get("NLK_MATCH_ORDER", "") in ("block", "1") and psz == 8
-                                          else "exact (the reference's hy, hx, c order)")},
-               "kernels_ms": {k_: round(v, 4) for k_, v in tm.items()},
-               "kernels_ms_note": "second loop of the same steps with HIP events around every kernel on the "
+        res["kernels_ms"] = {k_: round(v, 4) for k_, v in tm.items()}
+        res["kernels_ms_note"] = ("second loop of the same steps with HIP events around every kernel on the "
                                   "context's stream; ms_per_step is the timed (unprofiled) loop. Whole-frame calls "
                                   "of 8x8 patches replay the processed mask inside the group kernel's launch: "
                                   "commit_ms is the bit-plane kernel alone, group_ms includes the replay "
-                                  "(NLK_NO_CHASE=1: separate kernels)",
-               "roofline": roof}
+                                  "(NLK_NO_CHASE=1: separate kernels)")
+        res["roofline"] = roof
         if world == 1 and not striped and not args.no_extras and args.workload in ("C1", "C1L", "C2", "C3"):
             # beside the resident temporal call: the first frame of a sequence (deno0 = NULL: the spatial branch
             # everywhere, 441-candidate windows) and the drop-in API on host pointers (PCIe
@@ -1171,6 +1225,44 @@ def main():
             res["api_wall_ms"] = round(min(walls) * 1e3, 4)
             res["api_wall_note"] = ("nlkalman_filter_frame on pageable host images (75 MB up, 25 MB down at 1080p RGB), "
                                     f"best of {reps}; PCIe-inclusive, never `value`")
+        if args.workload == "C5":
+            res["kernels_ms"] = {k_: round(3 * v, 4) for k_, v in tm.items()}  # per step = 3 calls
+            res["stages_ms"] = {n_: {k_: round(v, 4) for k_, v in c5[n_]["ms"].items()} for n_ in c5}
+            res["roofline"] = c5_roofline(c5, w, h, ch, psz, ngx * ngy, ps)
+            if not args.no_cpu:
+                sys.path.insert(0, os.path.join(ROOT, "oracle"))
+                import oracle as O
+                res["cpu_baseline"] = cpu_baseline_chain(O, t_n1.cpu().numpy(), t_prev.cpu().numpy(), sigma, p, p2, ps)
+                res["speedup_vs_cpu"] = round(value / res["cpu_baseline"]["value"], 1)
+        if not args.no_cpu and args.workload != "C5":
+            sys.path.insert(0, os.path.join(ROOT, "oracle"))
+            import oracle as O
+            o1_h, prev_h = t_n1.cpu().numpy(), t_prev.cpu().numpy()
+            if world == 1:   # the CPU baseline is timed at N = 1 only; N > 1 keeps the parity leg below
+                ref, cb = cpu_baseline(O, o1_h, prev_h, sigma, p)
+                res["cpu_baseline"] = cb
+            else:
+                cb = None
+                if args.workload == "C3":   # (every other workload takes the serial order below)
+                    po = O.Params(*[getattr(p, k) for k, _ in p._fields_])
+                    ref = O.filter_frame(o1_h, prev_h, None, sigma, po, nthreads=min(os.cpu_count() or 1, 100))
+            # quality reference = the serial (OpenMP off) order, which is the order the GPU path
+            # reproduces; the threaded run above perturbs the processed-mask like the reference's
+            # own OpenMP build does. C3 never skips (step > temporal radius): any order is the same.
+            order = "parallel (order-independent for this config)"
+            if args.workload != "C3":
+                po = O.Params(*[getattr(p, k) for k, _ in p._fields_])
+                ref = O.filter_frame(o1_h, prev_h, None, sigma, po, nthreads=1)
+                order = "serial"
+            res["psnr_gpu_db"] = round(synth.psnr(O.opp2rgb(out), c1), 4)
+            res["psnr_cpu_db"] = round(synth.psnr(O.opp2rgb(ref), c1), 4)
+            res["psnr_delta_db"] = round(res["psnr_gpu_db"] - res["psnr_cpu_db"], 4)
+            res["psnr_reference_order"] = order
+            import numpy as np
+            res["max_abs_vs_cpu"] = round(float(np.abs(out - ref).max()), 6)
+            if cb is not None:
+                res["speedup_vs_cpu"] = round(value / cb["value"], 1)
+    if rank == 0:
         if args.strip_model and world == 1 and args.workload in ("C2", "C3"):
             model = []
             for nw in (2, 4, 8):
@@ -1221,43 +1313,7 @@ def main():
         if args.workload == "C5":
             res["config"]["workload"] = (f"C5: {w}x{h}x{ch} sigma={sigma:g}: flt1 temporal -> flt2 -> smo1 "
                                          f"(3 frame calls per step), frames resident")
-            res["kernels_ms"] = {k_: round(3 * v, 4) for k_, v in tm.items()}  # per step = 3 calls
-            res["stages_ms"] = {n_: {k_: round(v, 4) for k_, v in c5[n_]["ms"].items()} for n_ in c5}
-            res["roofline"] = c5_roofline(c5, w, h, ch, psz, ngx * ngy, ps)
             res["metric"] = "Mpix/s per frame (flt1 -> flt2 -> smo1 chain, 1080p sigma=20, frames resident)"
-            if not args.no_cpu:
-                sys.path.insert(0, os.path.join(ROOT, "oracle"))
-                import oracle as O
-                res["cpu_baseline"] = cpu_baseline_chain(O, t_n1.cpu().numpy(), t_prev.cpu().numpy(), sigma, p, p2, ps)
-                res["speedup_vs_cpu"] = round(value / res["cpu_baseline"]["value"], 1)
-        if not args.no_cpu and args.workload != "C5":
-            sys.path.insert(0, os.path.join(ROOT, "oracle"))
-            import oracle as O
-            o1_h, prev_h = t_n1.cpu().numpy(), t_prev.cpu().numpy()
-            if world == 1:   # the CPU baseline is timed at N = 1 only; N > 1 keeps the parity leg below
-                ref, cb = cpu_baseline(O, o1_h, prev_h, sigma, p)
-                res["cpu_baseline"] = cb
-            else:
-                cb = None
-                if args.workload == "C3":   # (every other workload takes the serial order below)
-                    po = O.Params(*[getattr(p, k) for k, _ in p._fields_])
-                    ref = O.filter_frame(o1_h, prev_h, None, sigma, po, nthreads=min(os.cpu_count() or 1, 100))
-            # quality reference = the serial (OpenMP off) order, which is the order the GPU path
-            # reproduces; the threaded run above perturbs the processed-mask like the reference's
-            # own OpenMP build does. C3 never skips (step > temporal radius): any order is the same.
-            order = "parallel (order-independent for this config)"
-            if args.workload != "C3":
-                po = O.Params(*[getattr(p, k) for k, _ in p._fields_])
-                ref = O.filter_frame(o1_h, prev_h, None, sigma, po, nthreads=1)
-                order = "serial"
-            res["psnr_gpu_db"] = round(synth.psnr(O.opp2rgb(out), c1), 4)
-            res["psnr_cpu_db"] = round(synth.psnr(O.opp2rgb(ref), c1), 4)
-            res["psnr_delta_db"] = round(res["psnr_gpu_db"] - res["psnr_cpu_db"], 4)
-            res["psnr_reference_order"] = order
-            import numpy as np
-            res["max_abs_vs_cpu"] = round(float(np.abs(out - ref).max()), 6)
-            if cb is not None:
-                res["speedup_vs_cpu"] = round(value / cb["value"], 1)
         emit(res)
     if world > 1:
         dist.destroy_process_group()

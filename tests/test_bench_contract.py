@@ -74,7 +74,7 @@ def test_bench_two_and_eight_ranks_on_one_gpu(n):
     whole-grid replay, accumulator halos, summed transform counts, own-row assembly, phase times."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1",
-                        "--phase-times"], capture_output=True, text=True, cwd=ROOT, env=dict(env, NLK_BENCH_ONE_GPU="1"),
+                        "--phase-times", "--full"], capture_output=True, text=True, cwd=ROOT, env=dict(env, NLK_BENCH_ONE_GPU="1"),
                        timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -182,7 +182,7 @@ def test_strip_selfcheck_at_one_gpu():
 
 @pytest.mark.gpu
 def test_default_bench_line():
-    d = _bench("--steps", "3", "--warmup", "1")
+    d = _bench("--steps", "3", "--warmup", "1", "--full")
     for k in REQUIRED:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
@@ -211,13 +211,59 @@ def test_default_bench_line():
 
 
 @pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run times the steps and prints the headline: the per-kernel, roofline, CPU and parity legs are --full's.
+    --dump-outputs writes the frame the last timed step computed."""
+    d = _bench("--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / "out"))
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "Mpix/s" and d["dtype"] == "f32"
+    assert "1080p" in d["metric"] and d["higher_is_better"] is True
+    assert abs(d["value"] - 1920 * 1080 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-2 * d["value"]
+    for k in ("roofline", "kernels_ms", "cpu_baseline", "psnr_delta_db", "first_frame_ms", "api_wall_ms"):
+        assert k not in d, k
+    import numpy as np
+    assert sorted(os.listdir(tmp_path / "out")) == ["denoised.npy"]
+    out = np.load(tmp_path / "out" / "denoised.npy")
+    assert out.dtype == np.float32 and out.shape == (1080, 1920, 3) and np.isfinite(out).all()
+    assert out.std() > 1.0                       # a filtered frame, not an untouched buffer
+
+
+def test_dumped_outputs_stay_within_their_budget(tmp_path):
+    """bench.dump_outputs: float32 files, whole arrays while they fit; beyond the budget the same seeded sample of
+    every array, so that two runs (two builds) are compared element for element."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    small = np.arange(12, dtype=np.float64).reshape(3, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"x": small})
+    got = np.load(tmp_path / "a" / "x.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = np.random.default_rng(1).standard_normal((2160, 3840, 3)).astype(np.float32)   # 4K RGB: 99.5 MB
+    for run in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / run), {"y": big, "z": big[:, :, :1]})
+    size = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert size <= 64e6 and size > 0.8 * bench.DUMP_BYTES
+    for f in ("y.npy", "z.npy"):
+        a, b = np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)
+        assert a.dtype == np.float32 and a.ndim == 1 and np.array_equal(a, b)
+
+
+def test_bench_options():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout and "--steps" in r.stdout
+
+
+@pytest.mark.gpu
 def test_strip_step_from_c_at_one_gpu():
     """--force-strips: the N > 1 step (enqueued from C over RCCL, csrc/strips.hip) with a world of one - what can be
     measured of it on a one-GPU box: its fixed cost over the whole-frame call, the host time to enqueue a step,
     the per-phase device times; with --strip-graph the step is replayed from a captured HIP graph."""
     plain = _bench("--steps", "20", "--warmup", "3", "--no-cpu")
     for extra in ((), ("--strip-graph",)):
-        d = _bench("--steps", "20", "--warmup", "3", "--no-cpu", "--force-strips", "--phase-times", *extra)
+        d = _bench("--steps", "20", "--warmup", "3", "--no-cpu", "--full", "--force-strips", "--phase-times", *extra)
         st = d["strip_step"]
         assert st["driver"].startswith("C (") and "rccl" in st["transport"]
         assert 0 < st["enqueue_us_per_step"] < 200
@@ -229,7 +275,7 @@ def test_strip_step_from_c_at_one_gpu():
 
 @pytest.mark.gpu
 def test_flow_bench_line():
-    d = _bench("--workload", "F1", "--steps", "2", "--warmup", "1")
+    d = _bench("--workload", "F1", "--steps", "2", "--warmup", "1", "--full")
     for k in REQUIRED:
         assert k in d, k
     assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1.0

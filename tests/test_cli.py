@@ -205,13 +205,27 @@ def test_image_io_against_pil(tools, tmp_path):
 # ------------------------------------------------------------ the tools behind a resident server
 
 import contextlib
+import pathlib
+import shutil
+import tempfile
 import time
 
 
+@pytest.fixture
+def sock_dir():
+    """A short directory for the server's socket: a unix socket's path must fit in sun_path (108 bytes), which a
+    deeply nested tmp_path need not (the server then refuses with "socket path too long")."""
+    d = tempfile.mkdtemp(prefix="nlk", dir="/tmp" if os.access("/tmp", os.W_OK) else None)
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 @contextlib.contextmanager
-def server(tmp_path, *flags, **more_env):
+def server(sock_dir, *flags, **more_env):
     """bin/nlk-server on a socket of its own; the tools find it through NLK_SERVER"""
-    sock = str(tmp_path / "nlk.sock")
+    sock = str(sock_dir / "nlk.sock")
     proc = subprocess.Popen([os.path.join(BIN, "nlk-server"), *flags, sock], stdout=subprocess.PIPE,
                             stderr=subprocess.PIPE, env=dict(os.environ, **more_env))
     try:
@@ -229,12 +243,12 @@ def server(tmp_path, *flags, **more_env):
             proc.kill()
 
 
-def test_tools_behind_the_resident_server_speak_the_same_grammar(tools, tmp_path):
+def test_tools_behind_the_resident_server_speak_the_same_grammar(tools, tmp_path, sock_dir):
     """NLK_SERVER=<socket>: the tool hands its arguments, directory, stdout and stderr to bin/nlk-server and
     exits with the status it returns (host/cli_server.h). Usage text, messages, exit codes and where they are
     printed must be what the tool prints by itself (reference: src/main-flt.c:71-149, lib/argparse); without a
     listener the tool works by itself; the server survives tools that leave through exit()."""
-    with server(tmp_path, "--lazy") as env:
+    with server(sock_dir, "--lazy") as env:
         for tool, args in (("nlkalman-flt", ["-h"]), ("nlkalman-smo", ["--help"]), ("nlkalman-flt", ["--nope"]),
                            ("nlkalman-smo", ["-s"]), ("nlkalman-flt", ["--f1_p", "x"]), ("nlkalman-flt", ["--f1_p", "0"]),
                            ("nlkalman-smo", ["--s1_p", "0", "--smo1", "x.tif"]), ("tvl1flow", []), ("decompose", []),
@@ -278,15 +292,15 @@ def test_tools_behind_the_resident_server_speak_the_same_grammar(tools, tmp_path
         fat.close()
         r = run("nlkalman-flt", "-h", env=env)
         assert r.returncode == 0 and r.stdout.startswith("Usage: nlkalman-flt")
-        r = run("nlkalman-flt", "-h", env=dict(env, NLK_SERVER=str(tmp_path / "nobody.sock")))
+        r = run("nlkalman-flt", "-h", env=dict(env, NLK_SERVER=str(sock_dir / "nobody.sock")))
         assert r.returncode == 0 and r.stdout.startswith("Usage: nlkalman-flt")     # no listener: by itself
-    r = subprocess.run([os.path.join(BIN, "nlk-server"), "--stop", str(tmp_path / "nlk.sock")], capture_output=True,
+    r = subprocess.run([os.path.join(BIN, "nlk-server"), "--stop", str(sock_dir / "nlk.sock")], capture_output=True,
                        text=True)
     assert r.returncode == 1 and "nobody listens" in r.stderr
 
 
 @pytest.mark.gpu
-def test_pipeline_through_the_resident_server(tools, tmp_path):
+def test_pipeline_through_the_resident_server(tools, tmp_path, sock_dir):
     """The steps scripts/nlkalman-seq.sh runs per frame (flow, first and second iteration, smoother) as separate
     processes - once by themselves, once with bin/nlk-server doing the work: the files written must be identical
     byte for byte (bit-reproducible aggregation on both sides: NLK_DETERMINISTIC), device memory must not pile up
@@ -316,7 +330,7 @@ def test_pipeline_through_the_resident_server(tools, tmp_path):
         return (time.perf_counter() - t0) / len(seq)
 
     alone = steps("a_", dict(os.environ, NLK_DETERMINISTIC="1"))
-    with server(tmp_path, NLK_DETERMINISTIC="1") as env:
+    with server(sock_dir, NLK_DETERMINISTIC="1") as env:
         steps("w_", env)                      # (code objects load on first use)
         served = min(steps("s_", env) for _ in range(3))
         for _ in range(40):                   # 200 more requests: what a request allocates is released

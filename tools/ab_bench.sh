@@ -8,7 +8,7 @@ for rep in 1 2; do
 for L in bwd-nlkalman_amd/ab/*.so; do
   cp $L bwd-nlkalman_amd/libnlk_hip.so
   echo -n "$(basename $L) (run $rep): "
-  python3 bench.py --no-cpu --steps 30 "$@" 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], {k: round(v, 4) for k, v in d['kernels_ms'].items()})"
+  python3 bench.py --full --no-cpu --steps 30 "$@" 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], {k: round(v, 4) for k, v in d['kernels_ms'].items()})"
 done
 done
 cp /tmp/libnlk_hip_current.so bwd-nlkalman_amd/libnlk_hip.so

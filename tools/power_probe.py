@@ -15,7 +15,7 @@ for h in hw:
         if f.startswith(("power", "freq", "temp1_input", "name")):
             print(" ", h, f, rd(os.path.join(h, f)))
 args = sys.argv[1:] or ["--steps", "4000", "--warmup", "50", "--no-cpu"]
-p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py")] + args, stdout=subprocess.PIPE, text=True)
+p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args, stdout=subprocess.PIPE, text=True)
 samples = []
 t0 = time.time()
 while p.poll() is None:
