@@ -35,6 +35,7 @@ HIP_SYMBOLS = [
     "nlk_strips_transport", "nlk_strips_load", "nlk_strips_set_options", "nlk_strips_step", "nlk_strips_sync",
     "nlk_strips_own_rows", "nlk_strips_ctx", "nlk_strips_geometry", "nlk_strips_stats", "nlk_strips_set_dry_run",
     "nlk_dev_strip_commit_group", "nlk_ctx_flush_active",
+    "nlk_dev_lz3_down", "nlk_dev_lz3_up", "nlk_dev_lz3_recompose_step",
 ]
 API_SYMBOLS = [
     "rgb2opp", "opp2rgb", "warp_bicubic", "nlkalman_default_params",
@@ -138,6 +139,9 @@ def hip():
         L.nlk_dev_occlusion_mask.argtypes = [vp, fp, fp, i, i, f]
         L.nlk_dev_image_dct.argtypes = [vp, fp, i, i, i, i]
         L.nlk_dev_copy_block.argtypes = [vp, fp, i, fp, i, i, i, i]
+        L.nlk_dev_lz3_down.argtypes = [vp, fp, fp, i, i, i]
+        L.nlk_dev_lz3_up.argtypes = [vp, fp, i, i, fp, i, i, i]
+        L.nlk_dev_lz3_recompose_step.argtypes = [vp, fp, fp, i, i, fp, i, i, i, f]
         L.nlk_host_tables.argtypes = [i, vp, vp, vp]
         L.nlk_ctx_set_deterministic.argtypes = [vp, i]
         L.nlk_ctx_reload_switches.argtypes = [vp]
@@ -285,6 +289,11 @@ def reload_switches():
 
 # ------------------------------------------------------- device-resident C-ABI
 
+class Lz3Levels(list):
+    """[(dptr, w, h)] of a Lanczos-3 pyramid, finest first; .ch = the channel count (Context.lz3_decompose)."""
+    ch = None
+
+
 class Context:
     """nlk_ctx wrapper: device pointers are plain ints (e.g. tensor.data_ptr())."""
 
@@ -392,6 +401,53 @@ class Context:
 
     def copy_block(self, d_dst, dw, d_src, sw, ch, bw, bh):
         self._chk(self.L.nlk_dev_copy_block(self.h, d_dst, dw, d_src, sw, ch, bw, bh))
+
+    # ---- Lanczos-3 pyramid (the lz3 multiscale pipeline's decompose / recompose; include/nlk_hip.h)
+    def lz3_down(self, d_dst, d_src, w, h, ch):
+        """d_dst (ceil(w/2) x ceil(h/2) x ch) = the Lanczos-3 half-band downsampling of d_src."""
+        self._chk(self.L.nlk_dev_lz3_down(self.h, d_dst, d_src, w, h, ch))
+
+    def lz3_up(self, d_dst, dw, dh, d_src, w, h, ch):
+        """d_dst (dw x dh x ch) = the 2x Lanczos-3 upsampling of d_src, fitted to dw, dh (2n - 1, 2n or 2n + 1)."""
+        self._chk(self.L.nlk_dev_lz3_up(self.h, d_dst, dw, dh, d_src, w, h, ch))
+
+    def lz3_recompose_step(self, d_out, d_yh, w, h, d_rl, wl, hl, ch, g=0.0):
+        """d_out = yh + up(gblur(rl - down(yh), g)) (w x h); rl is the recomposed coarser level."""
+        self._chk(self.L.nlk_dev_lz3_recompose_step(self.h, d_out, d_yh, w, h, d_rl, wl, hl, ch, float(g)))
+
+    def lz3_decompose(self, d_img, w, h, ch, levels):
+        """The pyramid of lanczos3_decompose: [(dptr, w, h)] for levels 0 .. levels - 1, level 0 being d_img itself
+        (not copied); the other levels are new allocations of the caller's. Nothing is synchronised."""
+        out = Lz3Levels([(d_img, w, h)])
+        out.ch = ch
+        for _ in range(1, levels):
+            d = self.alloc(((w + 1) // 2) * ((h + 1) // 2) * ch * 4)
+            self.lz3_down(d, out[-1][0], w, h, ch)
+            w, h = (w + 1) // 2, (h + 1) // 2
+            out.append((d, w, h))
+        return out
+
+    def lz3_recompose(self, levels, g=0.0, ch=None):
+        """R_0 of lanczos3_recompose from the levels [(dptr, w, h)], finest first (what lz3_decompose returns, or
+        the same shape of list with `ch` given): R_l = Y_l + up(gblur(R_{l+1} - down(Y_l), g)). Every level stays
+        resident and nothing waits for the device between levels; returns a new allocation (the levels are not
+        changed) of levels[0]'s size."""
+        ch = getattr(levels, "ch", None) if ch is None else ch
+        if ch is None:
+            raise ValueError("lz3_recompose: the channel count is unknown (pass ch=)")
+        r, rw, rh = levels[-1]
+        if len(levels) == 1:
+            out = self.alloc(rw * rh * ch * 4)
+            self.d2d(out, r, rw * rh * ch * 4)
+            return out
+        outs = [self.alloc(w * h * ch * 4) for (_, w, h) in levels[:-1]]
+        for l in range(len(levels) - 2, -1, -1):
+            y, w, h = levels[l]
+            self.lz3_recompose_step(outs[l], y, w, h, r, rw, rh, ch, g)
+            r, rw, rh = outs[l], w, h
+        for d in outs[1:]:   # (a free waits for the device: after the last level only)
+            self.free(d)
+        return outs[0]
 
     def frame_accumulate(self, d_acc, d_cur, d_prev, d_basic, w, h, ch, sigma, params, oy,
                          ngy, smoother=False):

@@ -89,6 +89,9 @@ struct nlk_ctx {
   NlkBuf chase;                   // in-launch mask replay: [0] the generation counter, from word 64 on the tagged decision
                                   // words (zeroed when allocated)
   NlkBuf ms;                      // whole-image DCT: temporary image + the two basis matrices
+  NlkBuf lz3;                     // Lanczos-3 recompose step: down(yh)
+  void* lz3_old[16] = {};         // ... its outgrown allocations, freed with the context (a free would synchronise the
+  int lz3_nold = 0;               //     device between the levels of a recompose)
   NlkBuf tv;                      // TV-L1 pyramids and work images
   NlkBuf slab, tflag;             // deterministic aggregation: per-tile accumulator slabs + "written" flags (k_gather.h)
   // host-pointer frame calls (nlk_frame_host): device copies of the caller's images, the streams the row bands

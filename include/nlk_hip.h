@@ -28,6 +28,8 @@
  *   nlk_dev_occlusion_mask              scripts/nlkalman-seq.sh:70-73 (plambda)
  *   nlk_dev_image_dct / nlk_dev_copy_block  lib/multiscale/multiscaler.cpp:21-107 and the
  *                                       coefficient copies of decompose / recompose
+ *   nlk_dev_lz3_down / _up / _recompose_step  lib/ms-lanczos3 (lanczos3_down, lanczos3_up and
+ *                                       one level of the recompose)
  */
 #ifndef NLK_HIP_H
 #define NLK_HIP_H
@@ -161,6 +163,22 @@ int nlk_dev_occlusion_mask(nlk_ctx *ctx, float *mask, const float *flow, int w, 
  * (decompose.cpp:40-46, recompose.cpp:43-49, merge_coarse.cpp:37-43). */
 int nlk_dev_image_dct(nlk_ctx *ctx, float *img, int w, int h, int ch, int inverse);
 int nlk_dev_copy_block(nlk_ctx *ctx, float *dst, int dw, const float *src, int sw, int ch, int bw, int bh);
+
+/* ---- Lanczos-3 pyramid of the lz3 multiscale pipeline (scripts/msnlkalman-lz3-seq.sh; the reference's
+ * lib/ms-lanczos3 tools; the operations are written out in DESIGN.md §9). HWC images, any w, h, ch >= 1;
+ * bit-reproducible (no atomics).
+ * nlk_dev_lz3_down: dst (ceil(w/2) x ceil(h/2)) = the 12-tap Lanczos-3 half-band downsampling of src.
+ * nlk_dev_lz3_up: dst (dw x dh) = the 2x Lanczos-3 upsampling of src (w x h), fitted to dw, dh: each must be
+ *   2n - 1 (last sample dropped), 2n or 2n + 1 (last sample repeated), else NLK_EINVAL.
+ * nlk_dev_lz3_recompose_step: one level of the recompose,
+ *   out (w x h) = yh + up(gblur(rl - down(yh), g), w, h)
+ *   with rl the recomposed coarser level (wl x hl = ceil(w/2) x ceil(h/2)) and gblur the separable Gaussian of
+ *   max(2 floor(g), 5) taps with a half-sample symmetric boundary (g = 0: none; 0 <= g < 33). Its down is
+ *   nlk_dev_lz3_down's kernel, so a level left as decomposed recomposes bit for bit. out may be yh, not rl. */
+int nlk_dev_lz3_down(nlk_ctx *ctx, float *dst, const float *src, int w, int h, int ch);
+int nlk_dev_lz3_up(nlk_ctx *ctx, float *dst, int dw, int dh, const float *src, int w, int h, int ch);
+int nlk_dev_lz3_recompose_step(nlk_ctx *ctx, float *out, const float *yh, int w, int h, const float *rl, int wl,
+                               int hl, int ch, float g);
 
 /* Row-strip form used by the multi-GPU driver. The images are a strip of the
  * frame (h rows) that already contains the search halo; targets are the patch
