@@ -36,6 +36,7 @@ HIP_SYMBOLS = [
     "nlk_strips_own_rows", "nlk_strips_ctx", "nlk_strips_geometry", "nlk_strips_stats", "nlk_strips_set_dry_run",
     "nlk_dev_strip_commit_group", "nlk_ctx_flush_active",
     "nlk_dev_lz3_down", "nlk_dev_lz3_up", "nlk_dev_lz3_recompose_step",
+    "nlk_dev_awgn", "nlk_dev_sqdiff_sum",
 ]
 API_SYMBOLS = [
     "rgb2opp", "opp2rgb", "warp_bicubic", "nlkalman_default_params",
@@ -142,6 +143,8 @@ def hip():
         L.nlk_dev_lz3_down.argtypes = [vp, fp, fp, i, i, i]
         L.nlk_dev_lz3_up.argtypes = [vp, fp, i, i, fp, i, i, i]
         L.nlk_dev_lz3_recompose_step.argtypes = [vp, fp, fp, i, i, fp, i, i, i, f]
+        L.nlk_dev_awgn.argtypes = [vp, fp, fp, C.c_size_t, f, C.c_uint32]
+        L.nlk_dev_sqdiff_sum.argtypes = [vp, vp, fp, fp, C.c_size_t]
         L.nlk_host_tables.argtypes = [i, vp, vp, vp]
         L.nlk_ctx_set_deterministic.argtypes = [vp, i]
         L.nlk_ctx_reload_switches.argtypes = [vp]
@@ -448,6 +451,25 @@ class Context:
         for d in outs[1:]:   # (a free waits for the device: after the last level only)
             self.free(d)
         return outs[0]
+
+    # ---- the ground-truth loop's noise and error measure (scripts/nlkalman-seq-gt.sh; include/nlk_hip.h)
+    def awgn(self, d_out, d_in, n, sigma, seed):
+        """d_out[i] = d_in[i] + sigma * N_i for i < n: what `SRAND=seed awgn sigma` writes (d_out may be d_in)."""
+        self._chk(self.L.nlk_dev_awgn(self.h, d_out, d_in, n, float(sigma), int(seed) & 0xFFFFFFFF))
+
+    def sqdiff_sum(self, d_sum, d_a, d_b, n):
+        """*d_sum (one device double) = sum of (a[i] - b[i])^2 over i < n in double, fixed order; not synchronised."""
+        self._chk(self.L.nlk_dev_sqdiff_sum(self.h, d_sum, d_a, d_b, n))
+
+    def mse(self, d_a, d_b, n):
+        """The mean of (a[i] - b[i])^2 over i < n (sqdiff_sum / n); waits for the device."""
+        d = self.alloc(8)
+        try:
+            self.sqdiff_sum(d, d_a, d_b, n)
+            s = float(self.download(d, (1,), np.float64)[0])
+        finally:
+            self.free(d)
+        return s / n
 
     def frame_accumulate(self, d_acc, d_cur, d_prev, d_basic, w, h, ch, sigma, params, oy,
                          ngy, smoother=False):

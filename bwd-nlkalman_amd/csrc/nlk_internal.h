@@ -93,6 +93,7 @@ struct nlk_ctx {
   void* lz3_old[16] = {};         // ... its outgrown allocations, freed with the context (a free would synchronise the
   int lz3_nold = 0;               //     device between the levels of a recompose)
   NlkBuf tv;                      // TV-L1 pyramids and work images
+  NlkBuf sqd;                     // nlk_dev_sqdiff_sum: the per-workgroup partials (fixed size)
   NlkBuf slab, tflag;             // deterministic aggregation: per-tile accumulator slabs + "written" flags (k_gather.h)
   // host-pointer frame calls (nlk_frame_host): device copies of the caller's images, the streams the row bands
   // travel on and the events that order them against the kernels

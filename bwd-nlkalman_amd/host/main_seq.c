@@ -25,9 +25,27 @@
  * File I/O runs beside the GPU: the output files (float TIFF / .flo / PNG encoding is most of a
  * frame's wall time) are written by a pool of threads from copies of the downloaded arrays, and
  * the next input frame is decoded while the current one is filtered. NLK_SEQ_IO_THREADS sets
- * the pool size (default 6; 0 = write in line). */
+ * the pool size (default 6; 0 = write in line).
+ *
+ * Built with NLK_SEQ_GT=1 the same source is `nlkalman-seq-gt`, the ground-truth loop of
+ * scripts/nlkalman-seq-gt.sh in one process:
+ *
+ *   nlkalman-seq-gt SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]
+ *     SEQ   printf pattern of the CLEAN frames; frame step 1; OPM defaults to
+ *           "1 0.40 0.75 1 0.40 0.75" (the gt script's own arguments and default)
+ *
+ * Each clean frame is uploaded, made noisy on the GPU (nlk_dev_awgn, seed SRAND + frame number, SRAND
+ * read from the environment as imscript's tools read it, default 0: the script's `SRAND=$RANDOM` is
+ * not reproducible) and written as OUT/%03d.tif - or, when that file already exists, the file is read
+ * and used (script lines 30-39). The recursion is nlkalman-seq's on the device noisy frame. Each RGB
+ * output is measured against the resident clean frame (nlk_dev_sqdiff_sum into one device array,
+ * downloaded at the end) and written as 8-bit flt1- / flt2- / smo1-%03d.png, the script's final
+ * state; OUT/measures gets the script's lines with its plambda arithmetic (write_measures), and stdout
+ * one line, the total MSEs as `printf "%f %f %f\n"`. */
 #include <errno.h>
+#include <math.h>
 #include <pthread.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -38,13 +56,18 @@
 #include "nlk_hip.h"
 #include "nlkalman.h"
 
+#ifndef NLK_SEQ_GT
+#define NLK_SEQ_GT 0
+#endif
+#define PROG (NLK_SEQ_GT ? "nlkalman-seq-gt" : "nlkalman-seq")
+
 nlk_ctx *nlkalman_hip_context(void); /* libnlkalman.so: the process-wide device context */
 
 static nlk_ctx *C;
 #define CHK(call)                                                    \
   do {                                                               \
     if ((call) != NLK_OK) {                                          \
-      fprintf(stderr, "nlkalman-seq: %s\n", nlk_last_error(C));      \
+      fprintf(stderr, "%s: %s\n", PROG, nlk_last_error(C));          \
       exit(1);                                                       \
     }                                                                \
   } while (0)
@@ -212,30 +235,118 @@ static char *path_of(const char *dir, const char *pattern, int i) {
   return full;
 }
 
-/* RGB copy of an opponent-space device frame -> file (takes ownership of `path`) */
-static void write_frame(char *path, const float *d_opp, float *d_tmp, int w, int h, int ch) {
+/* RGB copy of an opponent-space device frame -> file (takes ownership of `path`); d_sum != NULL: its squared
+ * error against d_clean goes to that device double first (the gt tool) */
+static void write_frame(char *path, const float *d_opp, float *d_tmp, int w, int h, int ch, double *d_sum,
+                        const float *d_clean) {
   const size_t bytes = (size_t)w * h * ch * sizeof(float);
   CHK(nlk_d2d(C, d_tmp, d_opp, bytes));
   CHK(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
+  if (d_sum) CHK(nlk_dev_sqdiff_sum(C, d_sum, d_clean, d_tmp, (size_t)w * h * ch));
   write_dev(path, d_tmp, w, h, ch);
 }
 
+/* ---- the gt tool's measures */
+
+/* SRAND as imscript's smapa.h reads it (sscanf "%lf", default 0), converted to the 32-bit seed as the
+ * reference's x86-64 build converts it (host/main_awgn.c) */
+static uint32_t srand_seed(void) {
+  const char *sv = getenv("SRAND");
+  double y;
+  if (!sv || sscanf(sv, "%lf", &y) != 1) return 0;
+  if (!(y > -9.2e18 && y < 9.2e18)) return 0;
+  return (uint32_t)(int64_t)y;
+}
+
+/* `plambda -c` as the script runs it: every number of the program is read as a float (strtof), every operation
+ * is done in double on floats and rounded to float, the result is printed "%.15lf" - and re-read from that text
+ * by the next call */
+static float pl_num(const char *s) { return strtof(s, NULL); }
+static void pl_out(char *s, float v) { sprintf(s, "%.15lf", (double)v); }
+static void pl_sqrt(char *out, const char *x) { pl_out(out, (float)sqrt((double)pl_num(x))); }
+static void pl_psnr(char *out, const char *rmse) { /* "255 RMSE / log10 20 *" */
+  const float q = (float)((double)255.f / (double)pl_num(rmse));
+  pl_out(out, (float)((double)(float)log10((double)q) * 20.0));
+}
+
+/* OUT/measures (scripts/nlkalman-seq-gt.sh:44-138) from the per-frame squared-error sums [pass][frame] of n
+ * samples; returns the total MSEs as printed (SS of each pass) in tot[pass] */
+static int write_measures(const char *out, const double *sums, int npass, int nframes, size_t n, char (*tot)[64]) {
+  static const char *label[3] = {"F1", "F2", "S1"};
+  char *path = path_of(out, "measures", 0);
+  FILE *f = fopen(path, "w");
+  if (!f) { perror(path); free(path); return 1; }
+  char m[64], rmse[64], psnr[64];
+  char *mm = malloc((size_t)nframes * 64 + 1), *pp = malloc((size_t)nframes * 64 + 1);
+  for (int p = 0; p < npass; ++p) {
+    char ss[64] = "0";
+    mm[0] = pp[0] = 0;
+    for (int t = 0; t < nframes; ++t) {
+      /* psnr.sh: MSE = imprintf "%v" (the mean, "%g"); the frame's RMSE and PSNR */
+      snprintf(m, sizeof m, "%g", sums[(size_t)p * nframes + t] / (double)n);
+      pl_sqrt(rmse, m);
+      pl_psnr(psnr, rmse);
+      sprintf(mm + strlen(mm), "%s%s", t ? " " : "", rmse);
+      sprintf(pp + strlen(pp), "%s%s", t ? " " : "", psnr);
+      /* SS = plambda -c "m n SS * + n+1 /" (the stack holds floats between the operations) */
+      const float prod = (float)((double)(float)t * (double)pl_num(ss));
+      const float sum = (float)((double)pl_num(m) + (double)prod);
+      pl_out(ss, (float)((double)sum / (double)(float)(t + 1)));
+    }
+    pl_sqrt(rmse, ss);
+    pl_psnr(psnr, rmse);
+    /* echo "F1 - Frame RMSE " ${MM[*]}: the label, a space, the list */
+    fprintf(f, "%s - Frame RMSE  %s\n%s - Frame PSNR  %s\n", label[p], mm, label[p], pp);
+    fprintf(f, "%s - Total RMSE %s\n%s - Total PSNR %s\n", label[p], rmse, label[p], psnr);
+    snprintf(tot[p], 64, "%s", ss);
+  }
+  free(mm);
+  free(pp);
+  const int bad = fclose(f) != 0;
+  if (bad) perror(path);
+  free(path);
+  return bad;
+}
+
+/* gt: every file written, then OUT/measures and the one stdout line (the script's `printf "%f %f %f\n"` of the
+ * total MSEs as plambda printed them; bash's printf reads them as long doubles) */
+static int finish_gt(const char *out, const double *d_sums, int npass, int nframes, size_t n) {
+  double *sums = malloc(sizeof(double) * 3 * nframes);
+  CHK(nlk_d2h(C, sums, d_sums, sizeof(double) * 3 * nframes));
+  int bad = wq_finish();
+  char tot[3][64];
+  bad |= write_measures(out, sums, npass, nframes, n, tot);
+  free(sums);
+  if (bad) return 1;
+  for (int p = 0; p < npass; ++p) printf(p ? " %Lf" : "%Lf", strtold(tot[p], NULL));
+  printf("\n");
+  return 0;
+}
+
 int main(int argc, const char **argv) {
+  const int gt = NLK_SEQ_GT;
   if (argc < 6) {
-    fprintf(stderr, "usage: %s SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]\n"
-                    "  one-process equivalent of scripts/nlkalman-seq.sh (see the header of main_seq.c)\n", argv[0]);
+    if (gt)
+      fprintf(stderr, "usage: %s SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
+                      "  one-process equivalent of scripts/nlkalman-seq-gt.sh (see the header of main_seq.c)\n", argv[0]);
+    else
+      fprintf(stderr, "usage: %s SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]\n"
+                      "  one-process equivalent of scripts/nlkalman-seq.sh (see the header of main_seq.c)\n", argv[0]);
     return 1;
   }
   const char *seq = argv[1], *out = argv[5];
   const int ffr = atoi(argv[2]), lfr = atoi(argv[3]);
   const float sigma = atof(argv[4]);
-  const int stp = argc > 6 && atoi(argv[6]) > 0 ? atoi(argv[6]) : 1;
-  const char *fpm = argc > 7 ? argv[7] : "", *spm = argc > 8 ? argv[8] : "";
-  const char *opm = argc > 9 && argv[9][0] ? argv[9] : "1 0.25 0.75 1 0.25 0.75";
+  /* the gt script has no STP: its FPM SPM OPM are $6 $7 $8 */
+  const int a0 = gt ? 6 : 7;
+  const int stp = !gt && argc > 6 && atoi(argv[6]) > 0 ? atoi(argv[6]) : 1;
+  const char *fpm = argc > a0 ? argv[a0] : "", *spm = argc > a0 + 1 ? argv[a0 + 1] : "";
+  const char *opm = argc > a0 + 2 && argv[a0 + 2][0] ? argv[a0 + 2]
+                    : gt ? "1 0.40 0.75 1 0.40 0.75" : "1 0.25 0.75 1 0.25 0.75";
   int fs1 = 1, fs2 = 1;
   float dw1 = 0.25f, th1 = 0.75f, dw2 = 0.25f, th2 = 0.75f;
   if (sscanf(opm, "%d %f %f %d %f %f", &fs1, &dw1, &th1, &fs2, &dw2, &th2) != 6) {
-    fprintf(stderr, "nlkalman-seq: OPM must hold 6 numbers: FSCALE1 DW1 TH1 FSCALE2 DW2 TH2\n");
+    fprintf(stderr, "%s: OPM must hold 6 numbers: FSCALE1 DW1 TH1 FSCALE2 DW2 TH2\n", PROG);
     return 1;
   }
   const int smoothing = strcmp(spm, "no") != 0;
@@ -309,6 +420,20 @@ int main(int argc, const char **argv) {
   float *d_flow = NULL, *d_occ = NULL, *flt1 = NULL;
   float **flt2 = calloc(nframes, sizeof(float *));  /* kept for the backward pass */
   struct nlk_tvl1_params of;
+  /* gt: the clean frames (all of them kept for the smoother's measures, else one buffer), the squared-error
+   * sums [pass][frame] (flt1, flt2, smo1) and the output names */
+  float **clean = calloc(nframes, sizeof(float *));
+  double *d_sums = NULL;
+  const uint32_t seed0 = gt ? srand_seed() : 0;
+  const char *ext = gt ? "png" : "tif";
+  char pat[64];
+#define OUTNAME(kind) (snprintf(pat, sizeof pat, "%s-%%03d.%s", kind, ext), pat)
+#define SUM(pass, t) (gt ? d_sums + (size_t)(pass) * nframes + (t) : NULL)
+  if (gt) {
+    void *d = NULL;
+    CHK(nlk_dev_alloc(C, &d, sizeof(double) * 3 * nframes));
+    d_sums = (double *)d;
+  }
 
   /* ---- forward pass (script lines 30-115) */
   int t = 0;
@@ -332,10 +457,34 @@ int main(int argc, const char **argv) {
         R.pinned_bytes = bytes;
       }
     } else if (w1 != w || h1 != h || c1 != ch) {
-      fprintf(stderr, "nlkalman-seq: %s: frame size differs from the first frame\n", name);
+      fprintf(stderr, "%s: %s: frame size differs from the first frame\n", PROG, name);
       return 1;
     }
-    CHK(nlk_h2d(C, d_rgb, fr, bytes));  /* (returns when the copy is done: the staging buffer is free again) */
+    if (!gt) {
+      CHK(nlk_h2d(C, d_rgb, fr, bytes));  /* (returns when the copy is done: the staging buffer is free again) */
+    } else {
+      /* the clean frame stays resident for the measures; the noisy one is OUT/%03d.tif if that exists (script
+       * lines 30-39), else clean + noise, written there */
+      clean[t] = smoothing || t == 0 ? dev_frame(bytes) : clean[0];
+      CHK(nlk_h2d(C, clean[t], fr, bytes));
+      char *npath = path_of(out, "%03d.tif", i);
+      struct stat st;
+      if (stat(npath, &st) == 0 && S_ISREG(st.st_mode)) {
+        int w2, h2, c2;
+        float *nz = img_read(npath, &w2, &h2, &c2);
+        if (!nz) return 1;
+        if (w2 != w || h2 != h || c2 != ch) {
+          fprintf(stderr, "%s: %s is %dx%dx%d, the clean frame %dx%dx%d\n", PROG, npath, w2, h2, c2, w, h, ch);
+          return 1;
+        }
+        CHK(nlk_h2d(C, d_rgb, nz, bytes));
+        free(nz);
+        free(npath);
+      } else {
+        CHK(nlk_dev_awgn(C, d_rgb, clean[t], (size_t)w * h * ch, sigma, seed0 + (uint32_t)i));
+        write_dev(npath, d_rgb, w, h, ch);
+      }
+    }
     if (fr != R.pinned) free(fr);
     if (i + stp <= lfr && Q.nthreads > 0) {  /* decode the next frame meanwhile */
       char next[1024];
@@ -367,20 +516,21 @@ int main(int argc, const char **argv) {
       write_dev(path_of(out, "bflo1-%03d.flo", i), d_flow, w, h, 2);
       write_dev(path_of(out, "bocc1-%03d.png", i), d_occ, w, h, 1);
     }
-    write_frame(path_of(out, "flt1-%03d.tif", i), n1, d_tmp, w, h, ch);
-    write_frame(path_of(out, "flt2-%03d.tif", i), n2, d_tmp, w, h, ch);
+    write_frame(path_of(out, OUTNAME("flt1"), i), n1, d_tmp, w, h, ch, SUM(0, t), clean[t]);
+    write_frame(path_of(out, OUTNAME("flt2"), i), n2, d_tmp, w, h, ch, SUM(1, t), clean[t]);
     if (flt1) nlk_dev_free(C, flt1);
     flt1 = n1;
     flt2[t] = n2;
     if (!smoothing && t > 0) { nlk_dev_free(C, flt2[t - 1]); flt2[t - 1] = NULL; }
     if (verbose) printf("frame %d filtered\n", i);
   }
-  if (!smoothing) return wq_finish(); /* script line 113 */
+  if (!smoothing) return gt ? finish_gt(out, d_sums, 2, nframes, (size_t)w * h * ch) : wq_finish(); /* script line 113 */
 
   /* ---- backward pass (script lines 117-150) */
   float **smo = calloc(nframes, sizeof(float *));
   smo[nframes - 1] = flt2[nframes - 1];
-  write_frame(path_of(out, "smo1-%03d.tif", ffr + (nframes - 1) * stp), smo[nframes - 1], d_tmp, w, h, ch);
+  write_frame(path_of(out, OUTNAME("smo1"), ffr + (nframes - 1) * stp), smo[nframes - 1], d_tmp, w, h, ch,
+              SUM(2, nframes - 1), clean[nframes - 1]);
   for (t = nframes - 2; t >= 0; --t) {
     const int i = ffr + t * stp;
     nlk_tvl1_default_params(&of);
@@ -400,8 +550,8 @@ int main(int argc, const char **argv) {
     CHK(nlk_dev_smooth_frame(C, smo[t], flt2[t], d_warp, NULL, w, h, ch, sigma, &s1));
     write_dev(path_of(out, "fflo-%03d.flo", i), d_flow, w, h, 2);
     write_dev(path_of(out, "focc-%03d.png", i), d_occ, w, h, 1);
-    write_frame(path_of(out, "smo1-%03d.tif", i), smo[t], d_tmp, w, h, ch);
+    write_frame(path_of(out, OUTNAME("smo1"), i), smo[t], d_tmp, w, h, ch, SUM(2, t), clean[t]);
     if (verbose) printf("frame %d smoothed\n", i);
   }
-  return wq_finish();
+  return gt ? finish_gt(out, d_sums, 3, nframes, (size_t)w * h * ch) : wq_finish();
 }

@@ -30,11 +30,16 @@
  *                                       coefficient copies of decompose / recompose
  *   nlk_dev_lz3_down / _up / _recompose_step  lib/ms-lanczos3 (lanczos3_down, lanczos3_up and
  *                                       one level of the recompose)
+ *   nlk_dev_awgn                        lib/imscript-lite/src/awgn.c (SRAND=seed awgn sigma in out),
+ *                                       scripts/nlkalman-seq-gt.sh:30-39
+ *   nlk_dev_sqdiff_sum                  the squared-error sum of scripts/psnr.sh:9 (plambda
+ *                                       "x y - 2 ^" | imprintf "%v"), times the sample count
  */
 #ifndef NLK_HIP_H
 #define NLK_HIP_H
 
 #include <stddef.h>
+#include <stdint.h>
 #include "nlkalman.h"
 
 #ifdef __cplusplus
@@ -179,6 +184,17 @@ int nlk_dev_lz3_down(nlk_ctx *ctx, float *dst, const float *src, int w, int h, i
 int nlk_dev_lz3_up(nlk_ctx *ctx, float *dst, int dw, int dh, const float *src, int w, int h, int ch);
 int nlk_dev_lz3_recompose_step(nlk_ctx *ctx, float *out, const float *yh, int w, int h, const float *rl, int wl,
                                int hl, int ch, float g);
+
+/* ---- noise and error measure of the ground-truth loop (scripts/nlkalman-seq-gt.sh). Both are
+ * asynchronous on the context's stream; n = 0 is allowed.
+ * nlk_dev_awgn: out[i] = in[i] + sigma * N_i (i < n, HWC order): what `SRAND=seed awgn sigma in out` writes
+ *   (lib/imscript-lite/src/awgn.c:24-26, random.c), bit for bit: the LCG reached by jump-ahead, the Box-Muller
+ *   cosine branch in double in the reference's expression order, no contraction. out may be in.
+ * nlk_dev_sqdiff_sum: *sum (one device double) = sum of (a[i] - b[i])^2 over i < n in double, in a fixed order
+ *   (bit-reproducible: no atomics). Sums of several calls may go to consecutive doubles of one buffer and be
+ *   downloaded once. */
+int nlk_dev_awgn(nlk_ctx *ctx, float *out, const float *in, size_t n, float sigma, uint32_t seed);
+int nlk_dev_sqdiff_sum(nlk_ctx *ctx, double *sum, const float *a, const float *b, size_t n);
 
 /* Row-strip form used by the multi-GPU driver. The images are a strip of the
  * frame (h rows) that already contains the search halo; targets are the patch
