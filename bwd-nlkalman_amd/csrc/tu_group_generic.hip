@@ -42,11 +42,19 @@ int launch_group_ch(nlk_ctx* c, const NlkGeom& g, const float* img, const float*
 
 }  // namespace
 
-// patch sizes 17..32, every channel count with ch * psz^2 <= 4096 (k_group_any.h)
+// patch sizes 17..32, and the lists of more than 128 entries that k_group is not instantiated for: every patch size and
+// channel count with ch * psz^2 <= 4096 (k_group_any.h)
 int nlk_launch_group_any(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev,
                          float* acc, const uint8_t* active) {
-  if (c->deterministic)
-    return fail(c, NLK_EUNSUP, "deterministic aggregation is not available for patch size %d with %d channels", g.psz, g.ch);
+  if (c->deterministic) {
+    if (g.psz > 16)
+      return fail(c, NLK_EUNSUP, "deterministic aggregation is not available for patches above 16 x 16 (patch size %d)",
+                  g.psz);
+    if (g.kmax > 128 || g.gstride > 128)
+      return fail(c, NLK_EUNSUP, "deterministic aggregation is not available for candidate lists of more than 128 "
+                                 "entries (k = %d, group size = %d)", g.kmax, g.gstride);
+    return fail(c, NLK_EUNSUP, "deterministic aggregation is not available in the generic group kernels (NLK_GENERIC_GROUP)");
+  }
   if (g.psz > 32 || g.E > NLK_ANY_EMAX)
     return fail(c, NLK_EUNSUP, "patch size %d with %d channels not supported (patches up to 32 x 32, ch * psz^2 <= %d)",
                 g.psz, g.ch, NLK_ANY_EMAX);
@@ -68,8 +76,9 @@ int nlk_launch_group_any(nlk_ctx* c, const NlkGeom& g, const float* img, const f
 int nlk_launch_group_generic(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur,
                              const float* prev, float* acc, const uint8_t* active) {
   if (c->deterministic)
-    return fail(c, NLK_EUNSUP, "deterministic aggregation is not available in the LDS-DCT kernel (candidate lists of "
-                               "more than 128 entries / NLK_GENERIC_GROUP)");
+    return fail(c, NLK_EUNSUP, "deterministic aggregation is not available for candidate lists of more than 128 "
+                               "entries (k = %d, group size = %d) or in the LDS-DCT kernel (NLK_GENERIC_GROUP)",
+                g.kmax, g.gstride);
   if (g.ch == 1) return launch_group_ch<1>(c, g, img, cur, prev, acc, active);
   if (g.ch == 3) return launch_group_ch<3>(c, g, img, cur, prev, acc, active);
   return fail(c, NLK_EUNSUP, "%d channels not supported (1 or 3)", g.ch);

@@ -224,6 +224,32 @@ def test_oracle_vs_numpy_restatement(O, synth, w, h, ch):
                        maxabs=2e-3)
 
 
+def test_oracle_vs_numpy_restatement_long_lists(O, synth):
+    """Lists and groups of 150 entries at sigma = 50 (above the 128 where the GPU path changes kernels,
+    tests/test_long_lists.py), from windows of up to 289 candidates: the reference side of those comparisons."""
+    w, h, ch, sigma = 40, 36, 3, 50.0
+    n0, n1 = _small(synth, w, h, ch, sigma, 150)
+    o0, o1 = O.rgb2opp(n0), O.rgb2opp(n1)
+    over = dict(search_sz_x=8, search_sz_t=7, npatches_x=150, npatches_t=150, npatches_tagg=150)
+    p1 = O.default_params(sigma, O.FLT1, **over)
+    p2 = O.default_params(sigma, O.FLT2, **over)
+    ps = O.default_params(sigma, O.SMO1, search_sz_t=7, npatches_t=150)
+    assert ps.npatches_tagg == 150
+    a, ta = O.filter_frame(o0, None, None, sigma, p1, trace=True)
+    assert ta["nsel"].max() == 150 and ta["nagg"].max() == 150
+    cases.assert_close(a, ref_numpy.frame(o0, None, None, sigma, p1.as_dict()), "flt1-x", maxabs=2e-3)
+    prev = a.copy()
+    prev[5:9, 7:12, :] = np.nan          # hole
+    prev[:, 0, :] = np.nan               # border column
+    b = O.filter_frame(o1, prev, None, sigma, p1)
+    cases.assert_close(b, ref_numpy.frame(o1, prev, None, sigma, p1.as_dict()), "flt1-t", maxabs=2e-3)
+    c = O.filter_frame(o1, prev, b, sigma, p2)
+    cases.assert_close(c, ref_numpy.frame(o1, prev, b, sigma, p2.as_dict()), "flt2-t", maxabs=2e-3)
+    d = O.smooth_frame(a, prev, None, sigma, ps)
+    cases.assert_close(d, ref_numpy.frame(a, prev, None, sigma, ps.as_dict(), smoother=True), "smo1",
+                       maxabs=2e-3)
+
+
 def test_oracle_openmp_close_to_serial(O, synth):
     """Thread-order perturbation of the processed mask moves PSNR by ~0.001 dB
     (SURVEY.md §8 note N1); the parallel mode is what bench.py times."""
