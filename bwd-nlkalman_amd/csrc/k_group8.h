@@ -367,6 +367,8 @@ k_group8(const float* __restrict__ img,   // matching / statistics image (planar
     }
 
     // ---------------- gains (reference: :799-811, :859-904; smoother :1683-1776)
+    // (the model of k_group_math.h, written out: through nlk_gain the smoother instantiations of this kernel
+    // come out of the compiler in another instruction order)
     // owner lanes hold the statistics the gain is made of: the previous-frame
     // lanes when np0 > 0 (Kalman / smoother), the image lanes otherwise (Wiener)
     const bool own = lane_on && (sel == (np0 > 0 ? 1 : 0));

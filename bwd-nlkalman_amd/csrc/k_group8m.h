@@ -37,6 +37,7 @@
 #include "nlk_common.h"
 #include "k_commit_rows.h"
 #include "k_group8.h"
+#include "k_group_math.h"
 #include <type_traits>
 
 typedef float nlk_f4 __attribute__((ext_vector_type(4)));
@@ -675,26 +676,9 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
             const float v0 = (T[3] - T[2] * T[2] * in0) * in0;  // previous-frame variance
             const float v01n = T[4] * in0;
             float a, term, m;
-            if (MODE == 2) {
-              const float v1 = (T[1] - T[0] * T[0] * in1) * in1;  // image variance
-              a = v1 * __builtin_amdgcn_rcpf(v1 + g.beta_t * v01n);
-              const float pv = v0 - g.beta_t * v01n;
-              term = (1 - a * a) * v1 + a * a * (pv > 0.f ? pv : 0.f);
-              m = 0.f;
-            } else if (MODE == 1) {
-              const float d = v01n - (g.have_basic ? 0.f : s2);
-              const float v = v0 + (0.f > d ? 0.f : d);
-              a = v * __builtin_amdgcn_rcpf(v + g.beta_t * s2);
-              term = (1 - a * a) * v + a * a * s2;
-              m = T[5] * ing - nx0q;
-            } else {
-              const float v1 = (T[1] - T[0] * T[0] * in1) * in1;
-              const float d = v1 - (g.have_basic ? 0.f : s2);
-              const float v = 0.f > d ? 0.f : d;
-              a = v * __builtin_amdgcn_rcpf(v + g.beta_x * s2);
-              term = a * v;
-              m = T[0] * in1 - nx0q;
-            }
+            const float v1 = (T[1] - T[0] * T[0] * in1) * in1;  // image variance
+            nlk_gain<MODE, true>(v1, v0, v01n, g, s2, a, term);
+            m = MODE == 2 ? 0.f : (MODE == 1 ? T[5] * ing : T[0] * in1) - nx0q;
             part_sum += term;
             // parked in LDS for pass B: [channel][gain | (1-a)*mean][quadrant][coefficient]
             // (filter: a*PG + (1-a)*M, reference: :879, :902)
@@ -737,25 +721,15 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
         if (MODE == 2) {
           const float v1 = (T[1] - T[0] * T[0] * in1) * in1;  // image variance
           const float v0 = (T[NS > 3 ? 3 : 0] - T[NS > 2 ? 2 : 0] * T[NS > 2 ? 2 : 0] * in0) * in0;  // previous-frame variance
-          const float v01n = T[NS > 4 ? 4 : 0] * in0;
-          a = v1 * __builtin_amdgcn_rcpf(v1 + g.beta_t * v01n);
-          const float pv = v0 - g.beta_t * v01n;
-          term = (1 - a * a) * v1 + a * a * (pv > 0.f ? pv : 0.f);
+          nlk_gain<2, true>(v1, v0, T[NS > 4 ? 4 : 0] * in0, g, s2, a, term);
           m = 0.f;
         } else if (MODE == 1) {
           const float v0 = (T[1] - T[0] * T[0] * in0) * in0;
-          const float v01n = T[NS > 2 ? 2 : 0] * in0;
-          const float d = v01n - (g.have_basic ? 0.f : s2);
-          const float v = v0 + (0.f > d ? 0.f : d);
-          a = v * __builtin_amdgcn_rcpf(v + g.beta_t * s2);
-          term = (1 - a * a) * v + a * a * s2;
+          nlk_gain<1, true>(0.f, v0, T[NS > 2 ? 2 : 0] * in0, g, s2, a, term);
           m = (T[0] - T[NS > 3 ? 3 : 0]) * ing - nx0q;
         } else {
           const float v1 = (T[1] - T[0] * T[0] * in1) * in1;
-          const float d = v1 - (g.have_basic ? 0.f : s2);
-          const float v = 0.f > d ? 0.f : d;
-          a = v * __builtin_amdgcn_rcpf(v + g.beta_x * s2);
-          term = a * v;
+          nlk_gain<0, true>(v1, 0.f, 0.f, g, s2, a, term);
           m = T[0] * in1 - nx0q;
         }
         part_sum += term;
@@ -1104,9 +1078,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
       inside[m] = __ballot(in || lane + 64 * m >= nagg);
     }
     // the reference adds the same per-coefficient terms once per group member
-    float vp = nlk_wave_sum_dpp(part_sum) * (float)nagg;
-    if (passthrough) vp = 0.f;
-    const float wgt = 1.f / (vp > 1e-6f ? vp : 1e-6f);
+    const float wgt = nlk_group_weight(nlk_wave_sum_dpp(part_sum), nagg, passthrough);
     float ww[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) ww[kk] = wgt * win[kk];

@@ -36,6 +36,7 @@
 #include "k_dct8.h"
 #include "k_group8.h"   // NlkGTile, nlk_f4u, nlk_wave_sum8
 #include "k_group8m.h"  // nlk_f4, nlk_bperm
+#include "k_group_math.h"
 #include "nlk_common.h"
 
 // ordering of this wavefront's LDS writes and reads: compiler-only (nlk_common.h); NLK_PP_WAITS
@@ -428,21 +429,13 @@ k_groupp(const float* __restrict__ img,   // matching / statistics image (planar
             const float v01n = tot[4][j] * in0;
             float ga, term, m;
             if (SMO) {
-              ga = v1 / (v1 + g.beta_t * v01n);
-              const float pv = v0 - g.beta_t * v01n;
-              term = (1 - ga * ga) * v1 + ga * ga * (pv > 0.f ? pv : 0.f);
+              nlk_gain<2, false>(v1, v0, v01n, g, s2, ga, term);
               m = 0.f;
             } else if (HP) {
-              const float d = v01n - (g.have_basic ? 0.f : s2);
-              const float v = v0 + (0.f > d ? 0.f : d);
-              ga = v / (v + g.beta_t * s2);
-              term = (1 - ga * ga) * v + ga * ga * s2;
+              nlk_gain<1, false>(v1, v0, v01n, g, s2, ga, term);
               m = x04[j] + tot5[j] * ing;
             } else {
-              const float d = v1 - (g.have_basic ? 0.f : s2);
-              const float v = 0.f > d ? 0.f : d;
-              ga = v / (v + g.beta_x * s2);
-              term = ga * v;
+              nlk_gain<0, false>(v1, v0, v01n, g, s2, ga, term);
               m = mean1;
             }
             if (PP == PSZ || 4 * slot + j < PSZ) part_sum += term;  // (padding coefficients own nothing)
@@ -459,9 +452,7 @@ k_groupp(const float* __restrict__ img,   // matching / statistics image (planar
     else pass_a(std::false_type{});
   }
   // the reference adds the same per-coefficient terms once per group member
-  float vp = nlk_wave_sum8(part_sum) * (float)nagg;
-  if (passthrough) vp = 0.f;
-  const float wgt = 1.f / (vp > 1e-6f ? vp : 1e-6f);
+  const float wgt = nlk_group_weight(nlk_wave_sum8(part_sum), nagg, passthrough);
   float ww[PB];
 #pragma unroll
   for (int e = 0; e < PB; ++e) ww[e] = wgt * wv[e];

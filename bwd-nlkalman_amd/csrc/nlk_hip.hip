@@ -75,14 +75,14 @@ int launch_group(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cu
   // Default: 8x8 patches with 1 or 3 channels on the matrix cores (k_group8m.h: 1.04 ms at C2 against
   // 1.34 ms for the packed-lane kernel), everything else on the packed-lane kernel (k_groupp.h; its
   // per-lane candidate lists hold up to 128 entries). Comparison variants: NLK_GROUP_PACKED=1 (8x8 on
-  // k_groupp), NLK_GROUP_DPP=1 (8x8: registers + DPP), NLK_GROUP12_ROWS=1 (12x12: lane = (channel,
-  // row)), NLK_GENERIC_GROUP=1 (LDS-DCT kernel). Lists of more than 128 entries (capacity k or group size) go to the
-  // LDS-DCT kernel (k_group.h) where it is instantiated - patch sizes 4 / 6 / 8 / 10 / 12 / 16 with 1 or 3 channels -
-  // and to k_group_any (patch size and channel count at run time, unbounded lists) otherwise, as patches above 16 do
+  // k_groupp), NLK_GROUP_DPP=1 (8x8: registers + DPP), NLK_GENERIC_GROUP=1 (LDS-DCT kernel). Lists of more than 128
+  // entries (capacity k or group size) go to the LDS-DCT kernel (k_group_lds.h): its fixed shapes where they are
+  // instantiated - patch sizes 4 / 6 / 8 / 10 / 12 / 16 with 1 or 3 channels - and its run-time shape (patch size and
+  // channel count from NlkGeom) otherwise, as patches above 16 do
   const bool ch13 = g.ch == 1 || g.ch == 3;
   const bool lists_fit = g.kmax <= 128 && g.gstride <= 128;
   const bool lds_dct = ch13 && (g.psz == 4 || g.psz == 6 || g.psz == 8 || g.psz == 10 || g.psz == 12 || g.psz == 16);
-  if (g.psz > 16) return nlk_launch_group_any(c, g, img, cur, prev, acc, active);  // (k_group_any.h: 17..32)
+  if (g.psz > 16) return nlk_launch_group_any(c, g, img, cur, prev, acc, active);  // (GroupAny: 17..32)
   if (nlk_set(c->sw.generic_group) || !lists_fit)
     return lds_dct ? nlk_launch_group_generic(c, g, img, cur, prev, acc, active)
                    : nlk_launch_group_any(c, g, img, cur, prev, acc, active);

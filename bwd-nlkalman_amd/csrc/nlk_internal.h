@@ -181,10 +181,11 @@ int nlk_launch_groupp_b(nlk_ctx* c, const NlkGeom& g, const float* img, const fl
                         float* acc, const uint8_t* active);
 int nlk_launch_groupp_c(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev,
                         float* acc, const uint8_t* active);
-// tu_group_generic.hip: the LDS-DCT kernel (even patch sizes, candidate lists of any length)
+// tu_group_generic.hip: the LDS-DCT kernel (k_group_lds.h), candidate lists of any length: its fixed shapes, patch
+// sizes 4 / 6 / 8 / 10 / 12 / 16 with 1 or 3 channels ...
 int nlk_launch_group_generic(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur,
                              const float* prev, float* acc, const uint8_t* active);
-// ... and the kernel for patch sizes 17..32 (k_group_any.h)
+// ... and its run-time shape: patch sizes up to 32, any channel count with ch * psz^2 <= 4096
 int nlk_launch_group_any(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev,
                          float* acc, const uint8_t* active);
 // tu_match.hip: block matching + selection (wide = the queued targets of a temporal frame)

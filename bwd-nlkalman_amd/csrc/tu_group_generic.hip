@@ -1,26 +1,21 @@
-// tu_group_generic.hip — launcher of the generic LDS-DCT group kernel (k_group.h), every patch size
-#include "k_group.h"
-#include "k_group_any.h"
+// tu_group_generic.hip — launchers of the LDS-DCT group kernel (k_group_lds.h): the fixed shapes 4 / 6 / 8 / 10 / 12 /
+// 16 with 1 or 3 channels, and the run-time shape for everything else up to 32 x 32
+#include "k_group_lds.h"
 #include "nlk_internal.h"
 
 namespace {
 
-template <int PSZ, int CH>
-int launch_group_t(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur,
-                   const float* prev, float* acc, const uint8_t* active) {
-  const int ngrid = g.ngx * g.ngy;
+template <class S>
+int launch_group_lds(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev, float* acc,
+                     const uint8_t* active, size_t lds) {
+  void (*kern)(const float*, const float*, const float*, const uint8_t*, NlkGeom, const uint32_t*, const NlkTarget*,
+               const uint32_t*, const uint8_t*, const float*, const float*, float*) =
+      g.smoother ? k_group_lds<S, true> : k_group_lds<S, false>;
+  if (lds) HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const float* basis = (const float*)c->tabs.p;
-  const float* window = basis + PSZ * PSZ;
-  if (g.smoother)
-    hipLaunchKernelGGL((k_group<PSZ, CH, true>), dim3(ngrid), dim3(64), 0, c->rv.stream, img,
-                       cur, prev, (const uint8_t*)c->vmap.p, g, (const uint32_t*)c->rv.topk,
-                       (const NlkTarget*)c->rv.tinfo, (const uint32_t*)c->rv.gcoords,
-                       active, basis, window, acc);
-  else
-    hipLaunchKernelGGL((k_group<PSZ, CH, false>), dim3(ngrid), dim3(64), 0, c->rv.stream, img,
-                       cur, prev, (const uint8_t*)c->vmap.p, g, (const uint32_t*)c->rv.topk,
-                       (const NlkTarget*)c->rv.tinfo, (const uint32_t*)c->rv.gcoords,
-                       active, basis, window, acc);
+  hipLaunchKernelGGL(kern, dim3(g.ngx * g.ngy), dim3(S::NT), lds, c->rv.stream, img, cur, prev,
+                     (const uint8_t*)c->vmap.p, g, (const uint32_t*)c->rv.topk, (const NlkTarget*)c->rv.tinfo,
+                     (const uint32_t*)c->rv.gcoords, active, basis, basis + g.p2, acc);
   HIPCHK(c, hipGetLastError());
   return NLK_OK;
 }
@@ -29,21 +24,20 @@ template <int CH>
 int launch_group_ch(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur,
                     const float* prev, float* acc, const uint8_t* active) {
   switch (g.psz) {
-    case 4: return launch_group_t<4, CH>(c, g, img, cur, prev, acc, active);
-    case 6: return launch_group_t<6, CH>(c, g, img, cur, prev, acc, active);
-    case 8: return launch_group_t<8, CH>(c, g, img, cur, prev, acc, active);
-    case 10: return launch_group_t<10, CH>(c, g, img, cur, prev, acc, active);
-    case 12: return launch_group_t<12, CH>(c, g, img, cur, prev, acc, active);
-    case 16: return launch_group_t<16, CH>(c, g, img, cur, prev, acc, active);
+    case 4: return launch_group_lds<GroupFixed<4, CH>>(c, g, img, cur, prev, acc, active, 0);
+    case 6: return launch_group_lds<GroupFixed<6, CH>>(c, g, img, cur, prev, acc, active, 0);
+    case 8: return launch_group_lds<GroupFixed<8, CH>>(c, g, img, cur, prev, acc, active, 0);
+    case 10: return launch_group_lds<GroupFixed<10, CH>>(c, g, img, cur, prev, acc, active, 0);
+    case 12: return launch_group_lds<GroupFixed<12, CH>>(c, g, img, cur, prev, acc, active, 0);
+    case 16: return launch_group_lds<GroupFixed<16, CH>>(c, g, img, cur, prev, acc, active, 0);
   }
   return fail(c, NLK_EUNSUP, "patch size %d not supported (4, 6, 8, 10, 12, 16)", g.psz);
 }
 
-
 }  // namespace
 
-// patch sizes 17..32, and the lists of more than 128 entries that k_group is not instantiated for: every patch size and
-// channel count with ch * psz^2 <= 4096 (k_group_any.h)
+// patch sizes 17..32, and the lists of more than 128 entries that the fixed shapes are not instantiated for: every
+// patch size and channel count with ch * psz^2 <= 4096 (GroupAny)
 int nlk_launch_group_any(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev,
                          float* acc, const uint8_t* active) {
   if (c->deterministic) {
@@ -58,19 +52,7 @@ int nlk_launch_group_any(nlk_ctx* c, const NlkGeom& g, const float* img, const f
   if (g.psz > 32 || g.E > NLK_ANY_EMAX)
     return fail(c, NLK_EUNSUP, "patch size %d with %d channels not supported (patches up to 32 x 32, ch * psz^2 <= %d)",
                 g.psz, g.ch, NLK_ANY_EMAX);
-  const int ngrid = g.ngx * g.ngy;
-  const float* basis = (const float*)c->tabs.p;
-  const float* window = basis + g.p2;
-  const size_t lds = sizeof(float) * (3 * (size_t)g.p2 + 4 * (size_t)g.E + NLK_ANY_NT / 64);
-  void (*kern)(const float*, const float*, const float*, const uint8_t*, NlkGeom, const uint32_t*, const NlkTarget*,
-               const uint32_t*, const uint8_t*, const float*, const float*, float*) =
-      g.smoother ? k_group_any<true> : k_group_any<false>;
-  HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(ngrid), dim3(NLK_ANY_NT), lds, c->rv.stream, img, cur, prev, (const uint8_t*)c->vmap.p, g,
-                     (const uint32_t*)c->rv.topk, (const NlkTarget*)c->rv.tinfo, (const uint32_t*)c->rv.gcoords, active,
-                     basis, window, acc);
-  HIPCHK(c, hipGetLastError());
-  return NLK_OK;
+  return launch_group_lds<GroupAny>(c, g, img, cur, prev, acc, active, GroupAny::lds_bytes(g));
 }
 
 int nlk_launch_group_generic(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur,

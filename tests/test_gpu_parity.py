@@ -156,7 +156,7 @@ def test_image_smaller_than_a_patch_is_returned_unchanged(ctx, built, O):
 @pytest.mark.parametrize("psz,ch,size", [(17, 1, (75, 61)), (20, 3, (90, 70)), (25, 3, (83, 77)), (32, 1, (100, 90)),
                                          (32, 3, (96, 80)), (8, 2, (60, 50)), (12, 4, (70, 64)), (7, 2, (41, 37))])
 def test_large_patches_and_other_channel_counts(ctx, built, O, psz, ch, size):
-    """Patch sizes 17..32 (`k_bm_generic` + `k_group_any`) and channel counts other than 1 and 3 (`k_bm_generic` +
+    """Patch sizes 17..32 (`k_bm_generic` + `k_group_lds<GroupAny>`) and channel counts other than 1 and 3 (`k_bm_generic` +
     `k_groupp`) - the reference takes any: src/nlkalman.c:524-525, 555-560: FLT1 spatial, FLT1 temporal with a NaN hole in the previous
     frame, FLT2 and the smoother against the serial oracle - records exact, pixels within tolerance."""
     rng = np.random.default_rng(100 * psz + ch)

@@ -1,11 +1,11 @@
 """Candidate lists and groups of more than 128 entries (-m gpu).
 
 Above 128 entries (list capacities: k = max(npatches_x, npatches_t), group = npatches_tagg) the group phase leaves
-the tuned kernels: patch sizes 4 / 6 / 8 / 10 / 12 / 16 with 1 or 3 channels go to the LDS-DCT kernel (k_group.h),
-every other shape to k_group_any (k_group_any.h). The smoother's default capacity, int(3 sigma - 15), crosses 128 at
-sigma = 48, so default parameters reach this path. The matcher sizes its per-wavefront list space by the
-capacities as well (nlk_hip.hip, plan_frame): 8 wavefronts, then 4, then k_bm_generic, which refuses above
-160 KiB of LDS.
+the tuned kernels: patch sizes 4 / 6 / 8 / 10 / 12 / 16 with 1 or 3 channels go to the fixed shapes of the LDS-DCT
+kernel (k_group_lds.h, GroupFixed), every other shape to its run-time shape (GroupAny). The smoother's default
+capacity, int(3 sigma - 15), crosses 128 at sigma = 48, so default parameters reach this path. The matcher sizes its
+per-wavefront list space by the capacities as well (nlk_hip.hip, plan_frame): 8 wavefronts, then 4, then
+k_bm_generic, which refuses above 160 KiB of LDS.
 
 Every case is compared with the serial oracle: integer records (k-NN lists, groups, np0, nagg, mask decisions)
 exactly, pixels within the bar of the neighbouring tests (tests/test_gpu_parity.py), excusing only the pixels whose
@@ -92,7 +92,7 @@ LENGTHS = [(psz, ch, size, n) for psz, ch, size in SHAPES for n in (128, 129)] +
 
 @pytest.mark.parametrize("psz,ch,size,n", LENGTHS, ids=[f"p{p}c{c}-n{n}" for p, c, _, n in LENGTHS])
 def test_list_length_boundary(ctx, built, O, psz, ch, size, n):
-    """List lengths on both sides of 128 (k_groupp / k_group8m below, k_group / k_group_any above), for the
+    """List lengths on both sides of 128 (k_groupp / k_group8m below, k_group_lds above), for the
     patch sizes and channel counts of every group route; lists really that long."""
     w, h = size
     t0, t1 = _four_modes(ctx, built, O, w, h, ch, 20.0, 1000 * psz + 10 * ch + n, f"p{psz} ch{ch} n{n}",
@@ -110,11 +110,11 @@ def test_capacity_alone_selects_the_long_route(ctx, built, O, over):
     assert max(t0["nagg"].max(), t1["nagg"].max()) < 128   # (short lists in long capacities)
 
 
-# ---------------------------------------------------------------- 2. k_group on the short lists
+# ---------------------------------------------------------------- 2. k_group_lds on the short lists
 
 @pytest.mark.parametrize("name", list(cases.CASES))
 def test_lds_dct_group_kernel_stagewise_vs_oracle_and_golden(built, O, monkeypatch, name):
-    """NLK_GENERIC_GROUP=1: the LDS-DCT kernel (k_group<PSZ, CH, SMO>) on the seeded cases, with the assertions of
+    """NLK_GENERIC_GROUP=1: the LDS-DCT kernel (k_group_lds<GroupFixed<PSZ, CH>, SMO>) on the seeded cases, with the assertions of
     test_pipeline_stagewise_vs_oracle_and_golden, golden files included."""
     monkeypatch.setenv("NLK_GENERIC_GROUP", "1")
     ref = cases.run_chain(O, name)
@@ -326,7 +326,7 @@ def test_smoother_tool_sigma50(built, O, tmp_path, extra):
     (7, dict(npatches_t=129, npatches_tagg=129), "more than 128 entries"),
     (20, dict(), "above 16 x 16")])
 def test_deterministic_mode_refuses_long_lists_and_large_patches(built, psz, over, cause):
-    """Deterministic aggregation exists for the tuned kernels only: a call that needs k_group / k_group_any stops
+    """Deterministic aggregation exists for the tuned kernels only: a call that needs k_group_lds stops
     with NLK_EUNSUP and a message that names the cause (long lists, or patches above 16), not the patch size."""
     sigma = 20.0
     f0, f1 = _frames(64, 56, 3, sigma, psz)
