@@ -37,6 +37,7 @@ HIP_SYMBOLS = [
     "nlk_dev_strip_commit_group", "nlk_ctx_flush_active",
     "nlk_dev_lz3_down", "nlk_dev_lz3_up", "nlk_dev_lz3_recompose_step",
     "nlk_dev_awgn", "nlk_dev_sqdiff_sum",
+    "nlk_sigma_default_params", "nlk_dev_estimate_sigma",
 ]
 API_SYMBOLS = [
     "rgb2opp", "opp2rgb", "warp_bicubic", "nlkalman_default_params",
@@ -62,6 +63,13 @@ class Params(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SigmaParams(C.Structure):
+    """struct nlk_sigma_params (include/nlk_hip.h): the noise-level estimator's block step, selected fraction and its
+    floor, and the two frequency bounds."""
+    _fields_ = [("step", C.c_int), ("frac", C.c_float), ("kmin", C.c_int), ("low_max", C.c_int),
+                ("high_min", C.c_int)]
 
 
 class Timings(C.Structure):
@@ -145,6 +153,9 @@ def hip():
         L.nlk_dev_lz3_recompose_step.argtypes = [vp, fp, fp, i, i, fp, i, i, i, f]
         L.nlk_dev_awgn.argtypes = [vp, fp, fp, C.c_size_t, f, C.c_uint32]
         L.nlk_dev_sqdiff_sum.argtypes = [vp, vp, fp, fp, C.c_size_t]
+        L.nlk_sigma_default_params.argtypes = [C.POINTER(SigmaParams)]
+        L.nlk_sigma_default_params.restype = None
+        L.nlk_dev_estimate_sigma.argtypes = [vp, fp, vp, fp, i, i, i, C.POINTER(SigmaParams)]
         L.nlk_host_tables.argtypes = [i, vp, vp, vp]
         L.nlk_ctx_set_deterministic.argtypes = [vp, i]
         L.nlk_ctx_reload_switches.argtypes = [vp]
@@ -219,6 +230,17 @@ def tvl1_params(w, h, **over):
         setattr(p, k, v)
     p.nscales = hip().nlk_tvl1_scales(w, h, p.nscales, p.zfactor)
     p.fscale = min(p.fscale, p.nscales)
+    return p
+
+
+def sigma_params(**over):
+    """nlk_sigma_default_params (step 4, frac 0.05, kmin 64, low_max 5, high_min 8) with fields overridden."""
+    p = SigmaParams()
+    hip().nlk_sigma_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in dict(p._fields_):
+            raise TypeError(f"sigma_params: no field {k!r}")
+        setattr(p, k, v)
     return p
 
 
@@ -470,6 +492,20 @@ class Context:
         finally:
             self.free(d)
         return s / n
+
+    # ---- the noise level of an image (include/nlk_hip.h: nlk_dev_estimate_sigma)
+    def estimate_sigma(self, d_img, w, h, ch, **params):
+        """(sigma, sigma_ch [ch] float32, counts [ch][2] int32 = blocks kept and blocks selected per channel) of the
+        device image d_img (HWC, 0..255 scale); params: the fields of SigmaParams. Waits for the device."""
+        p = sigma_params(**params)
+        d = self.alloc(4 * (1 + 3 * ch))
+        try:
+            self._chk(self.L.nlk_dev_estimate_sigma(self.h, d, d + 4 * (1 + ch), d_img, w, h, ch, C.byref(p)))
+            s = self.download(d, (1 + ch,))
+            counts = self.download(d + 4 * (1 + ch), (ch, 2), np.int32)
+        finally:
+            self.free(d)
+        return float(s[0]), s[1:].copy(), counts
 
     def frame_accumulate(self, d_acc, d_cur, d_prev, d_basic, w, h, ch, sigma, params, oy,
                          ngy, smoother=False):

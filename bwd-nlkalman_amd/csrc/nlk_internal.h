@@ -94,6 +94,7 @@ struct nlk_ctx {
   int lz3_nold = 0;               //     device between the levels of a recompose)
   NlkBuf tv;                      // TV-L1 pyramids and work images
   NlkBuf sqd;                     // nlk_dev_sqdiff_sum: the per-workgroup partials (fixed size)
+  NlkBuf sig;                     // nlk_dev_estimate_sigma: histograms, state, partials, keys (tu_sigma.hip)
   NlkBuf slab, tflag;             // deterministic aggregation: per-tile accumulator slabs + "written" flags (k_gather.h)
   // host-pointer frame calls (nlk_frame_host): device copies of the caller's images, the streams the row bands
   // travel on and the events that order them against the kernels

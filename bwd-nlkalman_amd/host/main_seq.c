@@ -5,7 +5,9 @@
  *   nlkalman-seq SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]
  *     SEQ   printf pattern of the noisy frames (e.g. in/%03d.tif)      (script: $1)
  *     FFR, LFR, STP  first / last frame, frame step (default 1)         ($2, $3, $6)
- *     SIG   noise standard deviation                                    ($4)
+ *     SIG   noise standard deviation, or "auto": measured on the first frame as the filter
+ *           sees it (nlk_dev_estimate_sigma) and printed as "sigma %.9g" on stdout before
+ *           that frame is filtered; the run is the one that number would have given  ($4)
  *     OUT   output folder: flt1-%03d.tif flt2-%03d.tif bflo1-%03d.flo bocc1-%03d.png and,
  *           unless SPM is "no", fflo-%03d.flo focc-%03d.png smo1-%03d.tif  ($5)
  *     FPM   extra nlkalman-flt options (--f1_p ... --f2_l ..., one string)  ($7)
@@ -41,7 +43,8 @@
  * output is measured against the resident clean frame (nlk_dev_sqdiff_sum into one device array,
  * downloaded at the end) and written as 8-bit flt1- / flt2- / smo1-%03d.png, the script's final
  * state; OUT/measures gets the script's lines with its plambda arithmetic (write_measures), and stdout
- * one line, the total MSEs as `printf "%f %f %f\n"`. */
+ * one line, the total MSEs as `printf "%f %f %f\n"`. With SIG = auto the noise level is measured on the first
+ * NOISY frame, and there is no sigma to make noise with: every OUT/%03d.tif must exist then. */
 #include <errno.h>
 #include <math.h>
 #include <pthread.h>
@@ -336,7 +339,8 @@ int main(int argc, const char **argv) {
   }
   const char *seq = argv[1], *out = argv[5];
   const int ffr = atoi(argv[2]), lfr = atoi(argv[3]);
-  const float sigma = atof(argv[4]);
+  const int auto_sigma = !strcmp(argv[4], "auto");
+  float sigma = auto_sigma ? 0.f : atof(argv[4]);
   /* the gt script has no STP: its FPM SPM OPM are $6 $7 $8 */
   const int a0 = gt ? 6 : 7;
   const int stp = !gt && argc > 6 && atoi(argv[6]) > 0 ? atoi(argv[6]) : 1;
@@ -396,9 +400,11 @@ int main(int argc, const char **argv) {
     fprintf(stderr, "nlkalman-seq: both filtering iterations are needed (f1_p, f2_p != 0)\n");
     return 1;
   }
-  nlkalman_default_params(&f1, sigma, FLT1);
-  nlkalman_default_params(&f2, sigma, FLT2);
-  nlkalman_default_params(&s1, sigma, SMO1);
+  if (!auto_sigma) { /* (auto: once the first frame is on the device) */
+    nlkalman_default_params(&f1, sigma, FLT1);
+    nlkalman_default_params(&f2, sigma, FLT2);
+    nlkalman_default_params(&s1, sigma, SMO1);
+  }
 
   /* every input frame must exist (script lines 19-28) */
   int nframes = 0;
@@ -480,6 +486,9 @@ int main(int argc, const char **argv) {
         CHK(nlk_h2d(C, d_rgb, nz, bytes));
         free(nz);
         free(npath);
+      } else if (auto_sigma) {
+        fprintf(stderr, "%s: SIG = auto needs the noisy frame %s (there is no sigma to make it with)\n", PROG, npath);
+        return 1;
       } else {
         CHK(nlk_dev_awgn(C, d_rgb, clean[t], (size_t)w * h * ch, sigma, seed0 + (uint32_t)i));
         write_dev(npath, d_rgb, w, h, ch);
@@ -490,6 +499,21 @@ int main(int argc, const char **argv) {
       char next[1024];
       snprintf(next, sizeof next, seq, i + stp);
       ra_start(next);
+    }
+    if (auto_sigma && t == 0) { /* the noise level of the first frame, then every default that depends on it */
+      float *d_sigma = dev_frame(sizeof(float) * (1 + ch));
+      CHK(nlk_dev_estimate_sigma(C, d_sigma, NULL, d_rgb, w, h, ch, NULL));
+      CHK(nlk_d2h(C, &sigma, d_sigma, sizeof(float)));
+      nlk_dev_free(C, d_sigma);
+      if (!(sigma > 0.f)) {
+        fprintf(stderr, "%s: SIG = auto: the first frame gives sigma = %g\n", PROG, (double)sigma);
+        return 1;
+      }
+      printf("sigma %.9g\n", (double)sigma);
+      fflush(stdout);
+      nlkalman_default_params(&f1, sigma, FLT1);
+      nlkalman_default_params(&f2, sigma, FLT2);
+      nlkalman_default_params(&s1, sigma, SMO1);
     }
     CHK(nlk_d2d(C, d_noisy, d_rgb, bytes));
     CHK(nlk_dev_rgb2opp(C, d_noisy, w, h, ch));

@@ -35,15 +35,18 @@ class SequenceFilter:
     """`ctx` = bwd-nlkalman_amd.Context. Flow parameters `of_*` are what the scripts pass to
     tvl1flow (lambda = "DW", finest scale, occlusion threshold: nlkalman-seq.sh:47-52); the defaults
     are the script's own OPM default "1 0.25 0.75 1 0.25 0.75" (nlkalman-seq.sh:12), as in host/main_seq.c
-    (nlkalman-seq-gt.sh uses DW = 0.40)."""
+    (nlkalman-seq-gt.sh uses DW = 0.40). sigma="auto": the noise level is measured on the first pushed frame
+    (Context.estimate_sigma on the RGB frame as pushed, what `nlkalman-seq ... auto` does); .sigma is None until then,
+    and the parameter sets not given are the defaults of the measured value."""
 
     def __init__(self, ctx, w, h, ch, sigma, f1=None, f2=None, s1=None, of_lambda=0.25, of_fscale=1,
                  occ_th=0.75, keep_history=True):
         pkg = _p()
-        self.ctx, self.w, self.h, self.ch, self.sigma = ctx, w, h, ch, float(sigma)
-        self.f1 = f1 or pkg.default_params(sigma, pkg.FLT1)
-        self.f2 = f2 or pkg.default_params(sigma, pkg.FLT2)
-        self.s1 = s1 or pkg.default_params(sigma, pkg.SMO1)
+        self.ctx, self.w, self.h, self.ch = ctx, w, h, ch
+        self.f1, self.f2, self.s1 = f1, f2, s1
+        self.sigma = None
+        if not (isinstance(sigma, str) and sigma == "auto"):
+            self._resolve(float(sigma))
         self.of = pkg.tvl1_params(w, h, lam=of_lambda, fscale=of_fscale)
         self.occ_th = float(occ_th)
         self.nbytes = w * h * ch * 4
@@ -58,6 +61,14 @@ class SequenceFilter:
         self.flow_iterations = []
         self.stage_s = None   # set to {} to have push() synchronise after each stage and add up its wall times (bench.py S1)
 
+    def _resolve(self, sigma):
+        """sigma is known: the parameter sets the caller left out are its defaults"""
+        pkg = _p()
+        self.sigma = sigma
+        self.f1 = self.f1 or pkg.default_params(sigma, pkg.FLT1)
+        self.f2 = self.f2 or pkg.default_params(sigma, pkg.FLT2)
+        self.s1 = self.s1 or pkg.default_params(sigma, pkg.SMO1)
+
     def _flow_and_mask(self, d_from_rgb, d_to_opp):
         """flow from frame `d_from_rgb` (RGB) to the frame whose opponent image is `d_to_opp`."""
         c, w, h, ch = self.ctx, self.w, self.h, self.ch
@@ -71,7 +82,13 @@ class SequenceFilter:
     def push(self, d_noisy_rgb):
         """Next noisy frame (device pointer, HWC RGB or gray, not modified). Afterwards
         self.flt1 / self.flt2 hold its two estimates (opponent space)."""
-        c, w, h, ch, sg = self.ctx, self.w, self.h, self.ch, self.sigma
+        c, w, h, ch = self.ctx, self.w, self.h, self.ch
+        if self.sigma is None:
+            est = c.estimate_sigma(d_noisy_rgb, w, h, ch)[0]
+            if not est > 0:
+                raise ValueError(f"SequenceFilter(sigma='auto'): the first frame gives sigma = {est}")
+            self._resolve(est)
+        sg = self.sigma
         c.d2d(self.d_noisy, d_noisy_rgb, self.nbytes)
         c.rgb2opp(self.d_noisy, w, h, ch)
         n1, n2 = self._frame(), self._frame()

@@ -34,6 +34,7 @@
  *                                       scripts/nlkalman-seq-gt.sh:30-39
  *   nlk_dev_sqdiff_sum                  the squared-error sum of scripts/psnr.sh:9 (plambda
  *                                       "x y - 2 ^" | imprintf "%v"), times the sample count
+ *   nlk_dev_estimate_sigma              nothing: the reference is told sigma; this measures it
  */
 #ifndef NLK_HIP_H
 #define NLK_HIP_H
@@ -195,6 +196,35 @@ int nlk_dev_lz3_recompose_step(nlk_ctx *ctx, float *out, const float *yh, int w,
  *   downloaded once. */
 int nlk_dev_awgn(nlk_ctx *ctx, float *out, const float *in, size_t n, float sigma, uint32_t seed);
 int nlk_dev_sqdiff_sum(nlk_ctx *ctx, double *sum, const float *a, const float *b, size_t n);
+
+/* ---- noise level of an image (restated in numpy by tests/sigma_ref.py): a block-DCT percentile
+ * estimator. HWC image on the 0..255 scale, w, h >= 8, ch >= 1; every channel by itself:
+ *   1. every 8 x 8 block with top-left (x, y), x % step == 0, y % step == 0, x <= w - 8, y <= h - 8; a block
+ *      holding a non-finite sample is skipped (warped frames carry NaN); N_c blocks are kept
+ *   2. Y = C B C^T, C the orthonormal DCT-II (the filter's basis at patch size 8)
+ *   3. L = the sum of Y[i][j]^2 over 1 <= i + j <= low_max
+ *   4. K = min(N_c, max(kmin, ceil(frac N_c))) (the product in double); T = the K-th smallest L, found exactly;
+ *      the selection is every block with L <= T, n_c >= K of them
+ *   5. the mean of Y[i][j]^2 over the selection for each (i, j) with i + j >= high_min, summed in double in an
+ *      order that depends on the sizes and parameters alone
+ *   6. sigma_c^2 = the median of those means (the mean of the two middle ones for an even count)
+ * and the pooled sigma = sqrt(mean_c sigma_c^2). Under white noise L and the high coefficients are independent,
+ * so selecting on L does not bias the means; on a textured image it picks the flat blocks.
+ * nlk_dev_estimate_sigma writes d_sigma[0] = sigma, d_sigma[1 + c] = sigma_c and, where d_counts is not NULL,
+ * d_counts[2c] = N_c, d_counts[2c + 1] = n_c (device arrays). Asynchronous on the context's stream; its scratch is
+ * kept in the context and grows on demand; the same input gives the same bits. A channel without a block gives
+ * sigma_c = NaN and the counts 0, 0 (the pooled value is then NaN). NLK_EINVAL for w < 8, h < 8, step < 1, frac
+ * outside (0, 1], low_max or high_min outside 1..14. prms = NULL: the defaults {4, 0.05, 64, 5, 8}. */
+struct nlk_sigma_params {
+  int step;      /* block grid step in pixels */
+  float frac;    /* fraction of the blocks selected ... */
+  int kmin;      /* ... and at least this many (all of them where there are fewer) */
+  int low_max;   /* L sums 1 <= i + j <= low_max */
+  int high_min;  /* the estimate uses i + j >= high_min */
+};
+void nlk_sigma_default_params(struct nlk_sigma_params *p);
+int nlk_dev_estimate_sigma(nlk_ctx *ctx, float *d_sigma, int *d_counts, const float *d_img, int w, int h, int ch,
+                           const struct nlk_sigma_params *prms);
 
 /* Row-strip form used by the multi-GPU driver. The images are a strip of the
  * frame (h rows) that already contains the search halo; targets are the patch
