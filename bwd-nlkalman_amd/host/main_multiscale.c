@@ -96,13 +96,16 @@ static int decompose(int argc, char **argv) {
   return EXIT_SUCCESS;
 }
 
-/* the first rows*factor x cols*factor coefficients of `from` replace those of `into` */
+/* the first rows*factor x cols*factor coefficients of `from` replace those of `into`; with factor > 1 the block
+ * is clipped to the coefficients that both images have (the reference reads and writes out of bounds there) */
 static void low_frequencies(struct dimg into, struct dimg from, float factor) {
+  if (from.ch != into.ch) {  /* (the copy walks both images with one channel count) */
+    fprintf(stderr, "multiscale: a level has %d channels, the image %d\n", from.ch, into.ch);
+    cli_exit(EXIT_FAILURE);
+  }
   int bh = 0, bw = 0;  /* loop bounds of recompose.cpp:43-44: j < rows * factor in float */
-  while (bh < from.h * factor) ++bh;
-  while (bw < from.w * factor) ++bw;
-  if (bh > into.h) bh = into.h;
-  if (bw > into.w) bw = into.w;
+  while (bh < from.h * factor && bh < from.h && bh < into.h) ++bh;
+  while (bw < from.w * factor && bw < from.w && bw < into.w) ++bw;
   CHK(nlk_dev_copy_block(C, into.d, into.w, from.d, from.w, from.ch, bw, bh));
 }
 

@@ -349,12 +349,14 @@ def ms_decompose(im, levels, ratio=2.0):
 
 def ms_recompose(levels, factor=0.8):
     """recompose (reference: lib/multiscale/recompose.cpp:24-56): the low frequencies of level 0
-    are replaced by those of the coarser levels (the first rows*factor x cols*factor of each)."""
+    are replaced by those of the coarser levels (the first rows*factor x cols*factor of each). With
+    factor > 1 the block is clipped to the coefficients both images have; the reference reads and writes
+    out of bounds there."""
     out = ms_dct(levels[0])
     for im in levels[1:]:
         co = ms_dct(im)
         f = np.float32(factor)
-        bh = int(np.ceil(np.float32(co.shape[0]) * f))
-        bw = int(np.ceil(np.float32(co.shape[1]) * f))
+        bh = min(int(np.ceil(np.float32(co.shape[0]) * f)), co.shape[0], out.shape[0])
+        bw = min(int(np.ceil(np.float32(co.shape[1]) * f)), co.shape[1], out.shape[1])
         out[:bh, :bw] = co[:bh, :bw]
     return ms_dct(out, inverse=True)
