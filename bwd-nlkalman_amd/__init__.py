@@ -38,6 +38,8 @@ HIP_SYMBOLS = [
     "nlk_dev_lz3_down", "nlk_dev_lz3_up", "nlk_dev_lz3_recompose_step",
     "nlk_dev_awgn", "nlk_dev_sqdiff_sum",
     "nlk_sigma_default_params", "nlk_dev_estimate_sigma",
+    "nlk_curve_default_params", "nlk_dev_estimate_noise_curve", "nlk_vst_scale", "nlk_dev_vst_forward",
+    "nlk_dev_vst_inverse", "nlk_dev_noise_affine",
 ]
 API_SYMBOLS = [
     "rgb2opp", "opp2rgb", "warp_bicubic", "nlkalman_default_params",
@@ -70,6 +72,16 @@ class SigmaParams(C.Structure):
     floor, and the two frequency bounds."""
     _fields_ = [("step", C.c_int), ("frac", C.c_float), ("kmin", C.c_int), ("low_max", C.c_int),
                 ("high_min", C.c_int)]
+
+
+class CurveParams(C.Structure):
+    """struct nlk_curve_params (include/nlk_hip.h): SigmaParams' fields, then the bins of the block mean (their number
+    and range) and the fewest blocks a bin needs."""
+    _fields_ = [("step", C.c_int), ("frac", C.c_float), ("kmin", C.c_int), ("low_max", C.c_int),
+                ("high_min", C.c_int), ("nbins", C.c_int), ("lo", C.c_float), ("hi", C.c_float), ("nmin", C.c_int)]
+
+
+CURVE_BIN = np.dtype([("nblocks", np.int32), ("nsel", np.int32), ("mean", np.float32), ("var", np.float32)])
 
 
 class Timings(C.Structure):
@@ -156,6 +168,14 @@ def hip():
         L.nlk_sigma_default_params.argtypes = [C.POINTER(SigmaParams)]
         L.nlk_sigma_default_params.restype = None
         L.nlk_dev_estimate_sigma.argtypes = [vp, fp, vp, fp, i, i, i, C.POINTER(SigmaParams)]
+        L.nlk_curve_default_params.argtypes = [C.POINTER(CurveParams)]
+        L.nlk_curve_default_params.restype = None
+        L.nlk_dev_estimate_noise_curve.argtypes = [vp, fp, vp, fp, i, i, i, C.POINTER(CurveParams)]
+        L.nlk_vst_scale.argtypes = [vp, i]
+        L.nlk_vst_scale.restype = f
+        L.nlk_dev_vst_forward.argtypes = [vp, fp, fp, C.c_size_t, i, vp, f]
+        L.nlk_dev_vst_inverse.argtypes = [vp, fp, fp, C.c_size_t, i, vp, f, i]
+        L.nlk_dev_noise_affine.argtypes = [vp, fp, fp, C.c_size_t, i, vp, C.c_uint32]
         L.nlk_host_tables.argtypes = [i, vp, vp, vp]
         L.nlk_ctx_set_deterministic.argtypes = [vp, i]
         L.nlk_ctx_reload_switches.argtypes = [vp]
@@ -242,6 +262,37 @@ def sigma_params(**over):
             raise TypeError(f"sigma_params: no field {k!r}")
         setattr(p, k, v)
     return p
+
+
+def curve_params(**over):
+    """nlk_curve_default_params (step 4, frac 0.1, kmin 32, low_max 5, high_min 8, nbins 16, lo 0, hi 256, nmin 32)
+    with fields overridden."""
+    p = CurveParams()
+    hip().nlk_curve_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in dict(p._fields_):
+            raise TypeError(f"curve_params: no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _ab(ab, ch):
+    """(a, b) for every channel, or [ch][2] -> a contiguous float32 [ch][2]"""
+    a = np.asarray(ab, np.float32)
+    a = np.tile(a, (ch, 1)) if a.ndim == 1 else a
+    if a.shape != (ch, 2):
+        raise ValueError(f"noise coefficients: want (a, b) or [{ch}][2], got shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def vst_scale(ab, ch=None):
+    """nlk_vst_scale: the common scale s = 255 / mean_c(span_c) of the variance-stabilising transform for the
+    coefficients ab ((a, b) with ch given, or [ch][2]); host-only."""
+    a = _ab(ab, ch if ch is not None else len(np.atleast_2d(ab)))
+    s = float(hip().nlk_vst_scale(a.ctypes.data, len(a)))
+    if not s > 0:
+        raise ValueError(f"vst_scale: refused coefficients {a.tolist()}")
+    return s
 
 
 def default_params(sigma, mode, **over):
@@ -506,6 +557,37 @@ class Context:
         finally:
             self.free(d)
         return float(s[0]), s[1:].copy(), counts
+
+    # ---- signal-dependent noise (include/nlk_hip.h: nlk_dev_estimate_noise_curve, nlk_dev_vst_*, nlk_dev_noise_affine)
+    def estimate_noise_curve(self, d_img, w, h, ch, **params):
+        """(ab [ch][2] float32 = (a_c, b_c) of var = a mean + b, bins [ch][nbins] of CURVE_BIN = N_q, n_q, m_q, v_q) of
+        the device image d_img (HWC, 0..255 scale); params: the fields of CurveParams. Waits for the device."""
+        p = curve_params(**params)
+        nb = max(int(p.nbins), 0)
+        d = self.alloc(8 * ch + 16 * ch * max(nb, 1))
+        try:
+            self._chk(self.L.nlk_dev_estimate_noise_curve(self.h, d, d + 8 * ch, d_img, w, h, ch, C.byref(p)))
+            ab = self.download(d, (ch, 2))
+            bins = self.download(d + 8 * ch, (ch, nb), CURVE_BIN)
+        finally:
+            self.free(d)
+        return ab, bins
+
+    def vst_forward(self, d_out, d_in, n, ch, ab, s):
+        """d_out[i] = the generalised Anscombe transform of d_in[i] with channel i mod ch's (a, b) and the scale s
+        (vst_scale); d_out may be d_in. Not synchronised."""
+        a = _ab(ab, ch)
+        self._chk(self.L.nlk_dev_vst_forward(self.h, d_out, d_in, n, ch, a.ctypes.data, float(s)))
+
+    def vst_inverse(self, d_out, d_in, n, ch, ab, s, mode=1):
+        """The inverse transform: mode 0 algebraic (exact), mode 1 with the closed-form unbiasing terms."""
+        a = _ab(ab, ch)
+        self._chk(self.L.nlk_dev_vst_inverse(self.h, d_out, d_in, n, ch, a.ctypes.data, float(s), int(mode)))
+
+    def noise_affine(self, d_out, d_in, n, ch, ab, seed):
+        """d_out[i] = d_in[i] + sqrt(max(a_c d_in[i] + b_c, 0)) N_i with awgn's deviates N_i (d_out may be d_in)."""
+        a = _ab(ab, ch)
+        self._chk(self.L.nlk_dev_noise_affine(self.h, d_out, d_in, n, ch, a.ctypes.data, int(seed) & 0xFFFFFFFF))
 
     def frame_accumulate(self, d_acc, d_cur, d_prev, d_basic, w, h, ch, sigma, params, oy,
                          ngy, smoother=False):

@@ -8,6 +8,14 @@
  *     SIG   noise standard deviation, or "auto": measured on the first frame as the filter
  *           sees it (nlk_dev_estimate_sigma) and printed as "sigma %.9g" on stdout before
  *           that frame is filtered; the run is the one that number would have given  ($4)
+ *           "vst" or "vst:A,B": signal-dependent noise var = a y + b. With "vst" the pair of every channel is
+ *           measured on the first frame as pushed (nlk_dev_estimate_noise_curve), with "vst:A,B" every channel
+ *           uses the given pair. One line "vst a_0 b_0 ... sigma S" (S = nlk_vst_scale, each value "%.9g") goes to
+ *           stdout before the first frame is filtered. Every noisy frame is transformed on the device
+ *           (nlk_dev_vst_forward) before anything else sees it, the whole recursion, flows included, runs on
+ *           transformed frames at sigma = S with the defaults of S, and every flt1 / flt2 / smo1 frame is
+ *           transformed back (nlk_dev_vst_inverse, mode 1) after opp2rgb, before it is downloaded. The gt tool
+ *           refuses these forms.
  *     OUT   output folder: flt1-%03d.tif flt2-%03d.tif bflo1-%03d.flo bocc1-%03d.png and,
  *           unless SPM is "no", fflo-%03d.flo focc-%03d.png smo1-%03d.tif  ($5)
  *     FPM   extra nlkalman-flt options (--f1_p ... --f2_l ..., one string)  ($7)
@@ -238,6 +246,9 @@ static char *path_of(const char *dir, const char *pattern, int i) {
   return full;
 }
 
+/* SIG = vst: the noise coefficients [ch][2] and the scale of the transform (vst_ab == NULL: no transform) */
+static float *vst_ab, vst_s;
+
 /* RGB copy of an opponent-space device frame -> file (takes ownership of `path`); d_sum != NULL: its squared
  * error against d_clean goes to that device double first (the gt tool) */
 static void write_frame(char *path, const float *d_opp, float *d_tmp, int w, int h, int ch, double *d_sum,
@@ -245,6 +256,7 @@ static void write_frame(char *path, const float *d_opp, float *d_tmp, int w, int
   const size_t bytes = (size_t)w * h * ch * sizeof(float);
   CHK(nlk_d2d(C, d_tmp, d_opp, bytes));
   CHK(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
+  if (vst_ab) CHK(nlk_dev_vst_inverse(C, d_tmp, d_tmp, (size_t)w * h * ch, ch, vst_ab, vst_s, 1));
   if (d_sum) CHK(nlk_dev_sqdiff_sum(C, d_sum, d_clean, d_tmp, (size_t)w * h * ch));
   write_dev(path, d_tmp, w, h, ch);
 }
@@ -339,7 +351,19 @@ int main(int argc, const char **argv) {
   }
   const char *seq = argv[1], *out = argv[5];
   const int ffr = atoi(argv[2]), lfr = atoi(argv[3]);
-  const int auto_sigma = !strcmp(argv[4], "auto");
+  const int vst = !strncmp(argv[4], "vst", 3); /* "vst" measures the curve, "vst:A,B" is told it */
+  float vst_a = 0.f, vst_b = 0.f;
+  if (vst && gt) {
+    fprintf(stderr, "%s: SIG = vst is not supported by the ground-truth loop\n", PROG);
+    return 1;
+  }
+  if (vst && argv[4][3] && (sscanf(argv[4] + 3, ":%f,%f", &vst_a, &vst_b) != 2 || !(vst_a >= 0.f) || !(vst_b >= 0.f) ||
+                            !(vst_a + vst_b > 0.f) || !(vst_a + vst_b <= 3e38f))) {
+    fprintf(stderr, "%s: SIG = %s: want vst or vst:A,B with A, B >= 0, not both 0\n", PROG, argv[4]);
+    return 1;
+  }
+  const int vst_given = vst && argv[4][3];
+  const int auto_sigma = vst || !strcmp(argv[4], "auto"); /* sigma is known once the first frame is on the device */
   float sigma = auto_sigma ? 0.f : atof(argv[4]);
   /* the gt script has no STP: its FPM SPM OPM are $6 $7 $8 */
   const int a0 = gt ? 6 : 7;
@@ -500,7 +524,31 @@ int main(int argc, const char **argv) {
       snprintf(next, sizeof next, seq, i + stp);
       ra_start(next);
     }
-    if (auto_sigma && t == 0) { /* the noise level of the first frame, then every default that depends on it */
+    if (vst && t == 0) { /* the noise curve of the first frame, the scale of its transform = the sigma of the run */
+      if (ch > 16) { fprintf(stderr, "%s: SIG = vst: %d channels are too many\n", PROG, ch); return 1; }
+      vst_ab = malloc(sizeof(float) * 2 * ch);
+      if (vst_given) {
+        for (int c = 0; c < ch; ++c) { vst_ab[2 * c] = vst_a; vst_ab[2 * c + 1] = vst_b; }
+      } else {
+        float *d_curve = dev_frame(sizeof(float) * 2 * ch);
+        CHK(nlk_dev_estimate_noise_curve(C, d_curve, NULL, d_rgb, w, h, ch, NULL));
+        CHK(nlk_d2h(C, vst_ab, d_curve, sizeof(float) * 2 * ch));
+        nlk_dev_free(C, d_curve);
+      }
+      sigma = vst_s = nlk_vst_scale(vst_ab, ch);
+      if (!(sigma > 0.f)) {
+        fprintf(stderr, "%s: SIG = vst: the first frame gives no noise curve (a_0 = %g, b_0 = %g)\n", PROG,
+                (double)vst_ab[0], (double)vst_ab[1]);
+        return 1;
+      }
+      printf("vst");
+      for (int c = 0; c < 2 * ch; ++c) printf(" %.9g", (double)vst_ab[c]);
+      printf(" sigma %.9g\n", (double)sigma);
+      fflush(stdout);
+      nlkalman_default_params(&f1, sigma, FLT1);
+      nlkalman_default_params(&f2, sigma, FLT2);
+      nlkalman_default_params(&s1, sigma, SMO1);
+    } else if (auto_sigma && t == 0) { /* the noise level of the first frame, then every default that depends on it */
       float *d_sigma = dev_frame(sizeof(float) * (1 + ch));
       CHK(nlk_dev_estimate_sigma(C, d_sigma, NULL, d_rgb, w, h, ch, NULL));
       CHK(nlk_d2h(C, &sigma, d_sigma, sizeof(float)));
@@ -515,6 +563,7 @@ int main(int argc, const char **argv) {
       nlkalman_default_params(&f2, sigma, FLT2);
       nlkalman_default_params(&s1, sigma, SMO1);
     }
+    if (vst) CHK(nlk_dev_vst_forward(C, d_rgb, d_rgb, (size_t)w * h * ch, ch, vst_ab, vst_s));
     CHK(nlk_d2d(C, d_noisy, d_rgb, bytes));
     CHK(nlk_dev_rgb2opp(C, d_noisy, w, h, ch));
     float *n1 = dev_frame(bytes), *n2 = dev_frame(bytes);

@@ -2,10 +2,11 @@
  * (nlk_dev_estimate_sigma, include/nlk_hip.h: a block-DCT percentile estimator; the reference has no such tool,
  * its users add the noise themselves and know sigma).
  *
- *   nlk-sigma [--step N] [--frac F] [--kmin N] FILE...
+ *   nlk-sigma [--step N] [--frac F] [--kmin N] [--curve [--nbins N] [--nmin N]] FILE...
  *
  * One line per file on stdout: FILE sigma sigma_0 ... sigma_{ch-1}, each value printed "%.9g" (a float read back
- * from that text is the same float). Status 1 with a usage line when no file is named, before any device is
+ * from that text is the same float). With --curve the line is FILE a_0 b_0 ... a_{ch-1} b_{ch-1}: the noise curve
+ * var = a mean + b of every channel (nlk_dev_estimate_noise_curve and its defaults). Status 1 with a usage line when no file is named, before any device is
  * opened; status 1 with a message for an unreadable file or a refused parameter. Behind NLK_SERVER like the
  * other tools. */
 #include <stdio.h>
@@ -27,18 +28,27 @@ static nlk_ctx *C;
     }                                                               \
   } while (0)
 
+#define USAGE "usage: %s [--step N] [--frac F] [--kmin N] [--curve [--nbins N] [--nmin N]] FILE...\n"
+
 int nlk_tool_sigma(int argc, const char **argv) {
   struct nlk_sigma_params p;
+  struct nlk_curve_params q;
   nlk_sigma_default_params(&p);
-  int a = 1;
-  for (; a + 1 < argc && !strncmp(argv[a], "--", 2); a += 2) {
-    if (!strcmp(argv[a], "--step")) p.step = atoi(argv[a + 1]);
-    else if (!strcmp(argv[a], "--frac")) p.frac = (float)atof(argv[a + 1]);
-    else if (!strcmp(argv[a], "--kmin")) p.kmin = atoi(argv[a + 1]);
+  nlk_curve_default_params(&q);
+  int a = 1, curve = 0, curve_only = 0;
+  while (a < argc && !strncmp(argv[a], "--", 2)) {
+    if (!strcmp(argv[a], "--curve")) { curve = 1; a += 1; continue; }
+    if (a + 1 >= argc) break;
+    if (!strcmp(argv[a], "--step")) p.step = q.step = atoi(argv[a + 1]);
+    else if (!strcmp(argv[a], "--frac")) p.frac = q.frac = (float)atof(argv[a + 1]);
+    else if (!strcmp(argv[a], "--kmin")) p.kmin = q.kmin = atoi(argv[a + 1]);
+    else if (!strcmp(argv[a], "--nbins")) { q.nbins = atoi(argv[a + 1]); curve_only = 1; }
+    else if (!strcmp(argv[a], "--nmin")) { q.nmin = atoi(argv[a + 1]); curve_only = 1; }
     else break;
+    a += 2;
   }
-  if (a >= argc || !strncmp(argv[a], "--", 2)) {
-    fprintf(stderr, "usage: %s [--step N] [--frac F] [--kmin N] FILE...\n", argc > 0 ? argv[0] : "nlk-sigma");
+  if (a >= argc || !strncmp(argv[a], "--", 2) || (curve_only && !curve)) {
+    fprintf(stderr, USAGE, argc > 0 ? argv[0] : "nlk-sigma");
     return EXIT_FAILURE;
   }
   for (; a < argc; ++a) {
@@ -51,14 +61,18 @@ int nlk_tool_sigma(int argc, const char **argv) {
     const size_t bytes = (size_t)w * h * ch * sizeof(float);
     C = nlkalman_hip_context();
     void *d_img = NULL, *d_sigma = NULL;
+    const int nval = curve ? 2 * ch : 1 + ch; /* values on the line */
     CHK(cli_dev_alloc(C, &d_img, bytes));
-    CHK(cli_dev_alloc(C, &d_sigma, (size_t)(1 + ch) * sizeof(float)));
+    CHK(cli_dev_alloc(C, &d_sigma, (size_t)nval * sizeof(float)));
     CHK(nlk_h2d(C, d_img, x, bytes));
-    CHK(nlk_dev_estimate_sigma(C, (float *)d_sigma, NULL, (const float *)d_img, w, h, ch, &p));
-    float *s = cli_host_keep(malloc((size_t)(1 + ch) * sizeof(float)));
-    CHK(nlk_d2h(C, s, d_sigma, (size_t)(1 + ch) * sizeof(float)));
+    if (curve)
+      CHK(nlk_dev_estimate_noise_curve(C, (float *)d_sigma, NULL, (const float *)d_img, w, h, ch, &q));
+    else
+      CHK(nlk_dev_estimate_sigma(C, (float *)d_sigma, NULL, (const float *)d_img, w, h, ch, &p));
+    float *s = cli_host_keep(malloc((size_t)nval * sizeof(float)));
+    CHK(nlk_d2h(C, s, d_sigma, (size_t)nval * sizeof(float)));
     printf("%s", argv[a]);
-    for (int i = 0; i <= ch; ++i) printf(" %.9g", (double)s[i]);
+    for (int i = 0; i < nval; ++i) printf(" %.9g", (double)s[i]);
     printf("\n");
     fflush(stdout);
     CHK(cli_dev_free(C, d_sigma));
@@ -71,7 +85,7 @@ int nlk_tool_sigma(int argc, const char **argv) {
 #ifndef NLK_TOOL_NO_MAIN
 int main(int argc, const char **argv) {
   if (argc < 2) { /* nothing to ask a server for either */
-    fprintf(stderr, "usage: %s [--step N] [--frac F] [--kmin N] FILE...\n", argv[0]);
+    fprintf(stderr, USAGE, argv[0]);
     return EXIT_FAILURE;
   }
   const int remote = cli_remote("nlk-sigma", argc, argv); /* a resident server (NLK_SERVER), if there is one */

@@ -21,6 +21,8 @@ Host side only: every array operation is a call of the C-ABI (include/nlk_hip.h)
 """
 import importlib
 
+import numpy as np
+
 _pkg = None
 
 
@@ -37,7 +39,12 @@ class SequenceFilter:
     are the script's own OPM default "1 0.25 0.75 1 0.25 0.75" (nlkalman-seq.sh:12), as in host/main_seq.c
     (nlkalman-seq-gt.sh uses DW = 0.40). sigma="auto": the noise level is measured on the first pushed frame
     (Context.estimate_sigma on the RGB frame as pushed, what `nlkalman-seq ... auto` does); .sigma is None until then,
-    and the parameter sets not given are the defaults of the measured value."""
+    and the parameter sets not given are the defaults of the measured value.
+    sigma="vst" or ("vst", a, b): signal-dependent noise var = a y + b, as `nlkalman-seq ... vst` / `vst:A,B`: the
+    pairs are measured on the first pushed frame (Context.estimate_noise_curve) or given for every channel; .noise
+    holds them ([ch][2] float32), .sigma the scale S of the variance-stabilising transform (vst_scale). Every pushed
+    frame is transformed first (Context.vst_forward), the recursion runs on transformed frames at sigma = S, and
+    download_rgb transforms back (Context.vst_inverse, mode 1)."""
 
     def __init__(self, ctx, w, h, ch, sigma, f1=None, f2=None, s1=None, of_lambda=0.25, of_fscale=1,
                  occ_th=0.75, keep_history=True):
@@ -45,7 +52,13 @@ class SequenceFilter:
         self.ctx, self.w, self.h, self.ch = ctx, w, h, ch
         self.f1, self.f2, self.s1 = f1, f2, s1
         self.sigma = None
-        if not (isinstance(sigma, str) and sigma == "auto"):
+        self.vst, self.noise, self.d_vst = False, None, None
+        if isinstance(sigma, str) and sigma == "vst":
+            self.vst = True
+        elif isinstance(sigma, (tuple, list)) and len(sigma) == 3 and sigma[0] == "vst":
+            self.vst = True
+            self._resolve_vst(np.tile(np.asarray(sigma[1:], np.float32), (ch, 1)))
+        elif not (isinstance(sigma, str) and sigma == "auto"):
             self._resolve(float(sigma))
         self.of = pkg.tvl1_params(w, h, lam=of_lambda, fscale=of_fscale)
         self.occ_th = float(occ_th)
@@ -69,6 +82,11 @@ class SequenceFilter:
         self.f2 = self.f2 or pkg.default_params(sigma, pkg.FLT2)
         self.s1 = self.s1 or pkg.default_params(sigma, pkg.SMO1)
 
+    def _resolve_vst(self, ab):
+        """the noise coefficients are known: the scale of the transform is the sigma of the run"""
+        self.noise = np.ascontiguousarray(ab, np.float32)
+        self._resolve(_p().vst_scale(self.noise))
+
     def _flow_and_mask(self, d_from_rgb, d_to_opp):
         """flow from frame `d_from_rgb` (RGB) to the frame whose opponent image is `d_to_opp`."""
         c, w, h, ch = self.ctx, self.w, self.h, self.ch
@@ -83,6 +101,13 @@ class SequenceFilter:
         """Next noisy frame (device pointer, HWC RGB or gray, not modified). Afterwards
         self.flt1 / self.flt2 hold its two estimates (opponent space)."""
         c, w, h, ch = self.ctx, self.w, self.h, self.ch
+        if self.vst:
+            if self.noise is None:
+                self._resolve_vst(c.estimate_noise_curve(d_noisy_rgb, w, h, ch)[0])
+            if self.d_vst is None:
+                self.d_vst = c.alloc(self.nbytes)
+            c.vst_forward(self.d_vst, d_noisy_rgb, w * h * ch, ch, self.noise, self.sigma)
+            d_noisy_rgb = self.d_vst   # the flow sees the transformed frame too
         if self.sigma is None:
             est = c.estimate_sigma(d_noisy_rgb, w, h, ch)[0]
             if not est > 0:
@@ -159,4 +184,6 @@ class SequenceFilter:
         c = self.ctx
         c.d2d(self.d_rgb, d_opp, self.nbytes)
         c.opp2rgb(self.d_rgb, self.w, self.h, self.ch)
+        if self.vst:
+            c.vst_inverse(self.d_rgb, self.d_rgb, self.w * self.h * self.ch, self.ch, self.noise, self.sigma, 1)
         return c.download(self.d_rgb, (self.h, self.w, self.ch))

@@ -39,6 +39,24 @@ def awgn(clean, sigma, seed):
     return out.astype(np.float32).reshape(clean.shape)
 
 
+def noise_affine(clean, ab, seed):
+    """clean + sqrt(max(a_c clean + b_c, 0)) * N(0,1), c the channel: signal-dependent noise with awgn's deviates
+    (nlk_dev_noise_affine restated). ab = (a, b) for every channel, or [ch][2]; the coefficients are float32."""
+    clean = np.ascontiguousarray(clean, np.float32)
+    ch = 1 if clean.ndim == 2 else clean.shape[2]
+    ab = np.asarray(ab, np.float32).astype(np.float64)
+    ab = np.tile(ab, (ch, 1)) if ab.ndim == 1 else ab
+    n = clean.size
+    u = lcg_stream(2 * n, seed).astype(np.float64) / 4294967295.0
+    with np.errstate(divide="ignore"):
+        g = np.sqrt(-2.0 * np.log(u[0::2])) * np.cos(2.0 * np.pi * u[1::2])
+    x = clean.reshape(-1, ch).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        sd = np.sqrt(np.maximum(ab[None, :, 0] * x + ab[None, :, 1], 0.0))
+    out = x + sd * g.reshape(-1, ch)
+    return out.astype(np.float32).reshape(clean.shape)
+
+
 def clean_frame(w, h, ch, t=0):
     """Sinusoids + checker blocks + a few hard edges, values in 0..255."""
     y, x = np.mgrid[0:h, 0:w].astype(np.float64)

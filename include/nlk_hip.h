@@ -35,6 +35,8 @@
  *   nlk_dev_sqdiff_sum                  the squared-error sum of scripts/psnr.sh:9 (plambda
  *                                       "x y - 2 ^" | imprintf "%v"), times the sample count
  *   nlk_dev_estimate_sigma              nothing: the reference is told sigma; this measures it
+ *   nlk_dev_estimate_noise_curve, nlk_dev_vst_forward / _inverse, nlk_dev_noise_affine
+ *                                       nothing: the reference knows white noise only
  */
 #ifndef NLK_HIP_H
 #define NLK_HIP_H
@@ -225,6 +227,72 @@ struct nlk_sigma_params {
 void nlk_sigma_default_params(struct nlk_sigma_params *p);
 int nlk_dev_estimate_sigma(nlk_ctx *ctx, float *d_sigma, int *d_counts, const float *d_img, int w, int h, int ch,
                            const struct nlk_sigma_params *prms);
+
+/* ---- signal-dependent noise, var(z | y) = a y + b (shot noise plus a read floor; restated in numpy
+ * by tests/curve_ref.py).
+ *
+ * nlk_dev_estimate_noise_curve measures (a_c, b_c) per channel: nlk_dev_estimate_sigma's estimator run per bin of
+ * the block mean, then a line through the bins. With the steps 1-3 of that estimator (blocks, Y, L):
+ *   2'. m = the sum of the block's 64 samples in double, in raster order, divided by 64
+ *   3'. the bin q = floor((m - lo) / (hi - lo) * nbins) in double (nbins - 1 at most); a block with m outside
+ *       [lo, hi) is skipped; N_q blocks are kept in bin q; a bin with N_q < nmin is dropped
+ *   4'. per bin K_q = min(N_q, max(kmin, ceil(frac N_q))) (the product in double) and the selection of the bin:
+ *       its blocks with L <= the K_q-th smallest L of the bin, found exactly; n_q of them. (One selection over the
+ *       frame would pick the dark blocks only.)
+ *   5'. v_q = the median over i + j >= high_min of the mean of Y[i][j]^2 over the selection, m_q = the mean of m over
+ *       it; sums in double in an order that depends on the sizes and parameters alone
+ *   6'. v = a m + b by least squares over the bins kept, weights n_q, in double. With fewer than 2 bins kept, or
+ *       sum n (m - mbar)^2 = 0, or a < 0: a = 0, b = sum n v / sum n. Then, if b < 0: a = sum n m v / sum n m^2,
+ *       b = 0. With no bin kept: a = b = NaN.
+ * d_curve[2c], d_curve[2c + 1] = (a_c, b_c); d_bins (may be NULL) [ch][nbins] receives N_q, n_q, m_q, v_q of every
+ * bin (n_q = 0 and m_q = v_q = NaN for a bin dropped or empty). Asynchronous on the context's stream; the scratch is
+ * kept in the context and grows on demand; the same input gives the same bits. NLK_EINVAL as nlk_dev_estimate_sigma,
+ * and for nbins outside 1..64, hi <= lo (or either not finite), nmin < 1, kmin < 1. prms = NULL: the defaults
+ * {4, 0.1, 32, 5, 8, 16, 0, 256, 32}. */
+struct nlk_curve_params {
+  int step;      /* block grid step in pixels */
+  float frac;    /* fraction of a bin's blocks selected ... */
+  int kmin;      /* ... and at least this many (all of them where there are fewer) */
+  int low_max;   /* L sums 1 <= i + j <= low_max */
+  int high_min;  /* the estimate uses i + j >= high_min */
+  int nbins;     /* bins of the block mean, 1..64 ... */
+  float lo, hi;  /* ... over [lo, hi) */
+  int nmin;      /* a bin needs this many blocks */
+};
+struct nlk_curve_bin {
+  int nblocks, nsel; /* N_q, n_q */
+  float mean, var;   /* m_q, v_q */
+};
+void nlk_curve_default_params(struct nlk_curve_params *p);
+int nlk_dev_estimate_noise_curve(nlk_ctx *ctx, float *d_curve, struct nlk_curve_bin *d_bins, const float *d_img,
+                                 int w, int h, int ch, const struct nlk_curve_params *prms);
+
+/* The generalised Anscombe transform that makes such noise white, per channel c = i mod ch of n samples, with the
+ * coefficients ab[2c], ab[2c + 1] = (a_c >= 0, b_c >= 0) (a HOST array) and one scale s for all channels. With
+ * u0 = 3 a^2 / 8 + b and u = a y + u0:
+ *   forward   g = (2 s / a) (sqrt(max(u, 0)) - sqrt(u0)), evaluated as 2 s y / (sqrt(u) + sqrt(u0)) for u > 0
+ *             (stable as a -> 0; s y / sqrt(b) at a = 0). The noise of g has standard deviation s in every channel.
+ *   inverse   r = max(g / s, -2 sqrt(u0) / a); mode 0: y = r sqrt(u0) + a r^2 / 4, the algebraic inverse
+ *             (inverse(forward(y)) = y); mode 1 adds the closed-form unbiasing terms of Makitalo and Foi,
+ *             a (1/4 + (1/4) sqrt(3/2) / D - (11/8) / D^2 + (5/8) sqrt(3/2) / D^3) with
+ *             D = max(2 (sqrt(u0) + a r / 2) / a, 2 sqrt(u0) / a); nothing for a = 0.
+ * float arithmetic; one pass; out may be in; NaN passes through; asynchronous on the context's stream. NLK_EINVAL
+ * for a negative or non-finite coefficient, a_c = b_c = 0, s not a positive finite number, ch outside 1..16, a mode
+ * other than 0 and 1.
+ * nlk_vst_scale (host only): s = 255 / mean_c(span_c), span_c = 2 * 255 / (sqrt(255 a_c + u0_c) + sqrt(u0_c)), the
+ * width of the transform of 0..255 at s = 1: with it a transformed frame keeps the 0..255 range that the filter's
+ * sigma-dependent default parameters were tuned on, and its noise level is s. NaN for coefficients the transforms
+ * refuse. */
+float nlk_vst_scale(const float *ab, int ch);
+int nlk_dev_vst_forward(nlk_ctx *ctx, float *out, const float *in, size_t n, int ch, const float *ab, float s);
+int nlk_dev_vst_inverse(nlk_ctx *ctx, float *out, const float *in, size_t n, int ch, const float *ab, float s,
+                        int mode);
+
+/* nlk_dev_awgn with a deviation that follows the signal: out[i] = (float)((double)in[i] + sqrt(max(a_c in[i] + b_c,
+ * 0)) g_i), c = i mod ch, g_i exactly the normal deviate nlk_dev_awgn draws for that index and seed; ab as above
+ * (host array, finite values, ch in 1..16). out may be in. */
+int nlk_dev_noise_affine(nlk_ctx *ctx, float *out, const float *in, size_t n, int ch, const float *ab,
+                         uint32_t seed);
 
 /* Row-strip form used by the multi-GPU driver. The images are a strip of the
  * frame (h rows) that already contains the search halo; targets are the patch
