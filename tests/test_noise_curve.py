@@ -79,6 +79,8 @@ PARITY = [
     (96, 64, 3, False, dict(nbins=1)),
     (96, 64, 3, False, dict(nbins=64, nmin=1)),  # histograms in HBM; bins of one block have K = N
     (96, 64, 3, False, dict(lo=64.0, hi=192.0)),  # blocks skipped by range
+    (256, 192, 1, False, dict(step=1, nbins=17)),  # 23 workgroup shares (more than the final kernel's 4 quarters), HBM histograms
+    (352, 240, 1, False, dict(step=1, frac=0.01)),  # 40 shares: more than its 32 partials in flight
 ]
 PARITY_IDS = ["%dx%dx%d%s%s" % (w, h, ch, "-holed" if holed else "", "".join(f"-{k}{v}" for k, v in p.items()))
               for w, h, ch, holed, p in PARITY]

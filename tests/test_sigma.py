@@ -67,6 +67,8 @@ PARITY = [
     (64, 48, 1, False, dict(step=8, frac=0.5, kmin=4)),   # (step 8: the blocks come straight from the image)
     (70, 53, 3, False, dict(step=8, frac=0.5, kmin=4)),
     (96, 64, 3, False, dict(frac=1.0)),                   # no selection
+    (256, 192, 1, False, dict(step=1, frac=0.01)),        # 23 workgroup shares: more than the final kernel's 4 quarters
+    (352, 240, 1, False, dict(step=1, frac=0.01)),        # 40 shares: more than its 32 partials in flight
 ]
 PARITY_IDS = ["%dx%dx%d%s%s" % (w, h, ch, "-holed" if holed else "", "".join(f"-{k}{v}" for k, v in p.items()))
               for w, h, ch, holed, p in PARITY]
