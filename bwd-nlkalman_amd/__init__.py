@@ -36,7 +36,7 @@ HIP_SYMBOLS = [
     "nlk_strips_own_rows", "nlk_strips_ctx", "nlk_strips_geometry", "nlk_strips_stats", "nlk_strips_set_dry_run",
     "nlk_dev_strip_commit_group", "nlk_ctx_flush_active",
     "nlk_dev_lz3_down", "nlk_dev_lz3_up", "nlk_dev_lz3_recompose_step",
-    "nlk_dev_awgn", "nlk_dev_sqdiff_sum",
+    "nlk_dev_awgn", "nlk_dev_sqdiff_sum", "nlk_dev_ssim",
     "nlk_sigma_default_params", "nlk_dev_estimate_sigma",
     "nlk_curve_default_params", "nlk_dev_estimate_noise_curve", "nlk_vst_scale", "nlk_dev_vst_forward",
     "nlk_dev_vst_inverse", "nlk_dev_noise_affine",
@@ -165,6 +165,7 @@ def hip():
         L.nlk_dev_lz3_recompose_step.argtypes = [vp, fp, fp, i, i, fp, i, i, i, f]
         L.nlk_dev_awgn.argtypes = [vp, fp, fp, C.c_size_t, f, C.c_uint32]
         L.nlk_dev_sqdiff_sum.argtypes = [vp, vp, fp, fp, C.c_size_t]
+        L.nlk_dev_ssim.argtypes = [vp, vp, fp, fp, fp, i, i, i, f]
         L.nlk_sigma_default_params.argtypes = [C.POINTER(SigmaParams)]
         L.nlk_sigma_default_params.restype = None
         L.nlk_dev_estimate_sigma.argtypes = [vp, fp, vp, fp, i, i, i, C.POINTER(SigmaParams)]
@@ -543,6 +544,28 @@ class Context:
         finally:
             self.free(d)
         return s / n
+
+    # ---- the quality measure (include/nlk_hip.h: nlk_dev_ssim)
+    def ssim_dev(self, d_ssim, d_map, d_a, d_b, w, h, ch, range=255.0):
+        """d_ssim[0] = the SSIM of the device images a (the reference) and b, d_ssim[1 + c] = that of channel c (device
+        doubles); d_map: None, or the (h - 10, w - 10, ch) float32 map. Not synchronised."""
+        self._chk(self.L.nlk_dev_ssim(self.h, d_ssim, d_map, d_a, d_b, w, h, ch, float(range)))
+
+    def ssim(self, d_a, d_b, w, h, ch, range=255.0, want_map=False):
+        """(ssim, ssim_ch [ch] float64) of the device images d_a (the reference) and d_b (HWC float32, dynamic range
+        `range`); with want_map also the (h - 10, w - 10, ch) float32 map of S. Waits for the device."""
+        nres, nmap = 1 + max(ch, 0), max(h - 10, 0) * max(w - 10, 0) * max(ch, 0)
+        d = self.alloc(8 * nres)
+        d_map = self.alloc(4 * max(nmap, 1)) if want_map else None
+        try:
+            self.ssim_dev(d, d_map, d_a, d_b, w, h, ch, range)
+            s = self.download(d, (nres,), np.float64)
+            smap = self.download(d_map, (h - 10, w - 10, ch)) if want_map else None
+        finally:
+            self.free(d)
+            if d_map is not None:
+                self.free(d_map)
+        return (float(s[0]), s[1:].copy(), smap) if want_map else (float(s[0]), s[1:].copy())
 
     # ---- the noise level of an image (include/nlk_hip.h: nlk_dev_estimate_sigma)
     def estimate_sigma(self, d_img, w, h, ch, **params):

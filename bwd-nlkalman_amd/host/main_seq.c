@@ -40,9 +40,14 @@
  * Built with NLK_SEQ_GT=1 the same source is `nlkalman-seq-gt`, the ground-truth loop of
  * scripts/nlkalman-seq-gt.sh in one process:
  *
- *   nlkalman-seq-gt SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]
+ *   nlkalman-seq-gt [--ssim] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]
  *     SEQ   printf pattern of the CLEAN frames; frame step 1; OPM defaults to
  *           "1 0.40 0.75 1 0.40 0.75" (the gt script's own arguments and default)
+ *     --ssim  (the script has no such thing) every output is also measured by nlk_dev_ssim, on the same two device
+ *           images as the squared error: OUT/measures-ssim gets, per pass, "F1 - Frame SSIM  v v ..." (the mean over
+ *           the channels of every frame) and "F1 - Total SSIM v" (their mean in double in frame order), each value
+ *           "%.9f", and stdout a second line "ssim T_F1 T_F2[ T_S1]". Frames must be at least 11 x 11 with at most
+ *           16 channels. Without the flag nothing of this happens: the same launches, files and stdout as before.
  *
  * Each clean frame is uploaded, made noisy on the GPU (nlk_dev_awgn, seed SRAND + frame number, SRAND
  * read from the environment as imscript's tools read it, default 0: the script's `SRAND=$RANDOM` is
@@ -250,14 +255,16 @@ static char *path_of(const char *dir, const char *pattern, int i) {
 static float *vst_ab, vst_s;
 
 /* RGB copy of an opponent-space device frame -> file (takes ownership of `path`); d_sum != NULL: its squared
- * error against d_clean goes to that device double first (the gt tool) */
+ * error against d_clean goes to that device double first (the gt tool), d_ssim != NULL: its SSIM and those of its
+ * channels to those 1 + ch device doubles (the gt tool with --ssim) */
 static void write_frame(char *path, const float *d_opp, float *d_tmp, int w, int h, int ch, double *d_sum,
-                        const float *d_clean) {
+                        double *d_ssim, const float *d_clean) {
   const size_t bytes = (size_t)w * h * ch * sizeof(float);
   CHK(nlk_d2d(C, d_tmp, d_opp, bytes));
   CHK(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
   if (vst_ab) CHK(nlk_dev_vst_inverse(C, d_tmp, d_tmp, (size_t)w * h * ch, ch, vst_ab, vst_s, 1));
   if (d_sum) CHK(nlk_dev_sqdiff_sum(C, d_sum, d_clean, d_tmp, (size_t)w * h * ch));
+  if (d_ssim) CHK(nlk_dev_ssim(C, d_ssim, NULL, d_clean, d_tmp, w, h, ch, 255.f));
   write_dev(path, d_tmp, w, h, ch);
 }
 
@@ -323,26 +330,71 @@ static int write_measures(const char *out, const double *sums, int npass, int nf
   return bad;
 }
 
+/* OUT/measures-ssim from the values [pass][frame][1 + ch] of nlk_dev_ssim: per pass the frames' SSIM (the mean over
+ * the channels) and their mean, in double in frame order; the totals also go to tot[pass] */
+static int write_ssim(const char *out, const double *v, int npass, int nframes, int ch, double *tot) {
+  static const char *label[3] = {"F1", "F2", "S1"};
+  char *path = path_of(out, "measures-ssim", 0);
+  FILE *f = fopen(path, "w");
+  if (!f) { perror(path); free(path); return 1; }
+  for (int p = 0; p < npass; ++p) {
+    double sum = 0.0;
+    fprintf(f, "%s - Frame SSIM ", label[p]);
+    for (int t = 0; t < nframes; ++t) {
+      const double s = v[((size_t)p * nframes + t) * (1 + ch)];
+      fprintf(f, " %.9f", s);
+      sum += s;
+    }
+    tot[p] = sum / (double)nframes;
+    fprintf(f, "\n%s - Total SSIM %.9f\n", label[p], tot[p]);
+  }
+  const int bad = fclose(f) != 0;
+  if (bad) perror(path);
+  free(path);
+  return bad;
+}
+
 /* gt: every file written, then OUT/measures and the one stdout line (the script's `printf "%f %f %f\n"` of the
- * total MSEs as plambda printed them; bash's printf reads them as long doubles) */
-static int finish_gt(const char *out, const double *d_sums, int npass, int nframes, size_t n) {
+ * total MSEs as plambda printed them; bash's printf reads them as long doubles); with --ssim (d_ssims != NULL) also
+ * OUT/measures-ssim and a second line, "ssim" and the total of every pass */
+static int finish_gt(const char *out, const double *d_sums, const double *d_ssims, int npass, int nframes, int ch,
+                     size_t n) {
   double *sums = malloc(sizeof(double) * 3 * nframes);
   CHK(nlk_d2h(C, sums, d_sums, sizeof(double) * 3 * nframes));
+  double *ssims = NULL, stot[3];
+  if (d_ssims) {
+    ssims = malloc(sizeof(double) * 3 * nframes * (1 + ch));
+    CHK(nlk_d2h(C, ssims, d_ssims, sizeof(double) * 3 * nframes * (1 + ch)));
+  }
   int bad = wq_finish();
   char tot[3][64];
   bad |= write_measures(out, sums, npass, nframes, n, tot);
+  if (ssims) bad |= write_ssim(out, ssims, npass, nframes, ch, stot);
   free(sums);
+  free(ssims);
   if (bad) return 1;
   for (int p = 0; p < npass; ++p) printf(p ? " %Lf" : "%Lf", strtold(tot[p], NULL));
   printf("\n");
+  if (d_ssims) {
+    printf("ssim");
+    for (int p = 0; p < npass; ++p) printf(" %.9f", stot[p]);
+    printf("\n");
+  }
   return 0;
 }
 
 int main(int argc, const char **argv) {
   const int gt = NLK_SEQ_GT;
+  int want_ssim = 0;
+  if (gt && argc > 1 && !strcmp(argv[1], "--ssim")) { /* the positional arguments follow it */
+    want_ssim = 1;
+    argv[1] = argv[0];
+    ++argv;
+    --argc;
+  }
   if (argc < 6) {
     if (gt)
-      fprintf(stderr, "usage: %s SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
+      fprintf(stderr, "usage: %s [--ssim] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
                       "  one-process equivalent of scripts/nlkalman-seq-gt.sh (see the header of main_seq.c)\n", argv[0]);
     else
       fprintf(stderr, "usage: %s SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]\n"
@@ -453,12 +505,13 @@ int main(int argc, const char **argv) {
   /* gt: the clean frames (all of them kept for the smoother's measures, else one buffer), the squared-error
    * sums [pass][frame] (flt1, flt2, smo1) and the output names */
   float **clean = calloc(nframes, sizeof(float *));
-  double *d_sums = NULL;
+  double *d_sums = NULL, *d_ssims = NULL; /* (d_ssims: [pass][frame][1 + ch], with --ssim only) */
   const uint32_t seed0 = gt ? srand_seed() : 0;
   const char *ext = gt ? "png" : "tif";
   char pat[64];
 #define OUTNAME(kind) (snprintf(pat, sizeof pat, "%s-%%03d.%s", kind, ext), pat)
 #define SUM(pass, t) (gt ? d_sums + (size_t)(pass) * nframes + (t) : NULL)
+#define SSIM(pass, t) (d_ssims ? d_ssims + ((size_t)(pass) * nframes + (t)) * (1 + ch) : NULL)
   if (gt) {
     void *d = NULL;
     CHK(nlk_dev_alloc(C, &d, sizeof(double) * 3 * nframes));
@@ -476,6 +529,16 @@ int main(int argc, const char **argv) {
     if (t == 0) {
       w = w1; h = h1; ch = c1;
       bytes = (size_t)w * h * ch * sizeof(float);
+      if (want_ssim) {
+        if (w < 11 || h < 11 || ch > 16) {
+          fprintf(stderr, "%s: --ssim needs frames of at least 11 x 11 with at most 16 channels, %s is %dx%dx%d\n", PROG,
+                  name, w, h, ch);
+          return 1;
+        }
+        void *d = NULL;
+        CHK(nlk_dev_alloc(C, &d, sizeof(double) * 3 * nframes * (1 + ch)));
+        d_ssims = (double *)d;
+      }
       d_rgb = dev_frame(bytes); d_noisy = dev_frame(bytes); d_tmp = dev_frame(bytes); d_warp = dev_frame(bytes);
       d_g0 = dev_frame((size_t)w * h * 4); d_g1 = dev_frame((size_t)w * h * 4); d_occ = dev_frame((size_t)w * h * 4);
       d_flow = dev_frame((size_t)w * h * 8);
@@ -589,21 +652,21 @@ int main(int argc, const char **argv) {
       write_dev(path_of(out, "bflo1-%03d.flo", i), d_flow, w, h, 2);
       write_dev(path_of(out, "bocc1-%03d.png", i), d_occ, w, h, 1);
     }
-    write_frame(path_of(out, OUTNAME("flt1"), i), n1, d_tmp, w, h, ch, SUM(0, t), clean[t]);
-    write_frame(path_of(out, OUTNAME("flt2"), i), n2, d_tmp, w, h, ch, SUM(1, t), clean[t]);
+    write_frame(path_of(out, OUTNAME("flt1"), i), n1, d_tmp, w, h, ch, SUM(0, t), SSIM(0, t), clean[t]);
+    write_frame(path_of(out, OUTNAME("flt2"), i), n2, d_tmp, w, h, ch, SUM(1, t), SSIM(1, t), clean[t]);
     if (flt1) nlk_dev_free(C, flt1);
     flt1 = n1;
     flt2[t] = n2;
     if (!smoothing && t > 0) { nlk_dev_free(C, flt2[t - 1]); flt2[t - 1] = NULL; }
     if (verbose) printf("frame %d filtered\n", i);
   }
-  if (!smoothing) return gt ? finish_gt(out, d_sums, 2, nframes, (size_t)w * h * ch) : wq_finish(); /* script line 113 */
+  if (!smoothing) return gt ? finish_gt(out, d_sums, d_ssims, 2, nframes, ch, (size_t)w * h * ch) : wq_finish(); /* script line 113 */
 
   /* ---- backward pass (script lines 117-150) */
   float **smo = calloc(nframes, sizeof(float *));
   smo[nframes - 1] = flt2[nframes - 1];
   write_frame(path_of(out, OUTNAME("smo1"), ffr + (nframes - 1) * stp), smo[nframes - 1], d_tmp, w, h, ch,
-              SUM(2, nframes - 1), clean[nframes - 1]);
+              SUM(2, nframes - 1), SSIM(2, nframes - 1), clean[nframes - 1]);
   for (t = nframes - 2; t >= 0; --t) {
     const int i = ffr + t * stp;
     nlk_tvl1_default_params(&of);
@@ -623,8 +686,8 @@ int main(int argc, const char **argv) {
     CHK(nlk_dev_smooth_frame(C, smo[t], flt2[t], d_warp, NULL, w, h, ch, sigma, &s1));
     write_dev(path_of(out, "fflo-%03d.flo", i), d_flow, w, h, 2);
     write_dev(path_of(out, "focc-%03d.png", i), d_occ, w, h, 1);
-    write_frame(path_of(out, OUTNAME("smo1"), i), smo[t], d_tmp, w, h, ch, SUM(2, t), clean[t]);
+    write_frame(path_of(out, OUTNAME("smo1"), i), smo[t], d_tmp, w, h, ch, SUM(2, t), SSIM(2, t), clean[t]);
     if (verbose) printf("frame %d smoothed\n", i);
   }
-  return gt ? finish_gt(out, d_sums, 3, nframes, (size_t)w * h * ch) : wq_finish();
+  return gt ? finish_gt(out, d_sums, d_ssims, 3, nframes, ch, (size_t)w * h * ch) : wq_finish();
 }

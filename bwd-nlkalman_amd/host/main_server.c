@@ -2,7 +2,7 @@
  *
  *   nlk-server [--lazy] <socket>     serve nlkalman-flt, nlkalman-smo, tvl1flow and the multiscale tools
  *                                    (decompose, recompose, merge_coarse, lanczos3_decompose,
- *                                    lanczos3_recompose), awgn and nlk-sigma on that unix socket
+ *                                    lanczos3_recompose), awgn, nlk-sigma and nlk-measure on that unix socket
  *   nlk-server --stop <socket>       ask the server there to leave
  *
  * The tools find it through NLK_SERVER=<socket>; scripts/nlkalman-seq.sh (reference: :39-41, 80-81, 100-102) runs
@@ -24,6 +24,7 @@ int nlk_tool_multiscale(int argc, const char **argv);
 int nlk_tool_lanczos3(int argc, const char **argv);
 int nlk_tool_awgn(int argc, const char **argv);
 int nlk_tool_sigma(int argc, const char **argv);
+int nlk_tool_measure(int argc, const char **argv);
 
 int main(int argc, const char **argv) {
   int lazy = 0, stop = 0;
@@ -43,7 +44,7 @@ int main(int argc, const char **argv) {
       {"nlkalman-flt", nlk_tool_flt}, {"nlkalman-smo", nlk_tool_smo}, {"tvl1flow", nlk_tool_tvl1},
       {"decompose", nlk_tool_multiscale}, {"recompose", nlk_tool_multiscale}, {"merge_coarse", nlk_tool_multiscale},
       {"lanczos3_decompose", nlk_tool_lanczos3}, {"lanczos3_recompose", nlk_tool_lanczos3}, {"awgn", nlk_tool_awgn},
-      {"nlk-sigma", nlk_tool_sigma}, {NULL, NULL}};
+      {"nlk-sigma", nlk_tool_sigma}, {"nlk-measure", nlk_tool_measure}, {NULL, NULL}};
   if (!lazy) (void)nlkalman_hip_context();
   return cli_serve(path, tools);
 }

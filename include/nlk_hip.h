@@ -37,6 +37,7 @@
  *   nlk_dev_estimate_sigma              nothing: the reference is told sigma; this measures it
  *   nlk_dev_estimate_noise_curve, nlk_dev_vst_forward / _inverse, nlk_dev_noise_affine
  *                                       nothing: the reference knows white noise only
+ *   nlk_dev_ssim                        nothing: the reference measures the squared error only
  */
 #ifndef NLK_HIP_H
 #define NLK_HIP_H
@@ -198,6 +199,31 @@ int nlk_dev_lz3_recompose_step(nlk_ctx *ctx, float *out, const float *yh, int w,
  *   downloaded once. */
 int nlk_dev_awgn(nlk_ctx *ctx, float *out, const float *in, size_t n, float sigma, uint32_t seed);
 int nlk_dev_sqdiff_sum(nlk_ctx *ctx, double *sum, const float *a, const float *b, size_t n);
+
+/* ---- quality measure (restated in numpy by tests/ssim_ref.py): the structural similarity of Wang,
+ * Bovik, Sheikh and Simoncelli (2004) in its usual form: Gaussian window, population moments, valid region.
+ *   Inputs     a (the reference) and b: HWC float32 images, w >= 11, h >= 11, 1 <= ch <= 16; range = the dynamic
+ *              range L, positive and finite (the tools use 255)
+ *   Window     g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0..10, divided by its sum, made in double on the host; the
+ *              2-D weight is g[i] g[j]
+ *   Moments    every channel by itself. At each of the (w - 10)(h - 10) valid positions 5 <= x < w - 5,
+ *              5 <= y < h - 5 the five window moments mu_a, mu_b, E[a^2], E[b^2], E[ab] are accumulated in double over
+ *              the 121 samples, separably (rows, then columns); the float samples are converted first, so every
+ *              product of two samples is exact
+ *   Variances  var_a = E[a^2] - mu_a^2, var_b likewise, cov = E[ab] - mu_a mu_b
+ *   Constants  C1 = (0.01 L)^2, C2 = (0.03 L)^2
+ *   Value      S = (2 mu_a mu_b + C1)(2 cov + C2) / ((mu_a^2 + mu_b^2 + C1)(var_a + var_b + C2)), in double
+ *   Pooling    ssim_c = the mean of S over the valid positions of channel c; ssim = the mean of the ssim_c
+ * Sums are in double, in an order that depends on w, h, ch alone, without atomics: the same input gives the same bits
+ * on every call. Non-finite samples are not special-cased: every position whose window holds one gets a non-finite S
+ * (its channel's mean and ssim are then NaN), and no other position is affected.
+ * d_ssim[0] = ssim, d_ssim[1 + c] = ssim_c (device doubles; several calls may write to consecutive slots of one
+ * buffer that is downloaded once, as with nlk_dev_sqdiff_sum). d_map may be NULL; otherwise it is [h - 10][w - 10][ch]
+ * float32 and receives S of every position. Asynchronous on the context's stream; the scratch is kept in the context
+ * and grows on demand. NLK_EINVAL for w < 11, h < 11, ch outside 1..16, a range that is not positive and finite, or
+ * a NULL pointer other than d_map; the context keeps working after a refused call. */
+int nlk_dev_ssim(nlk_ctx *ctx, double *d_ssim, float *d_map, const float *d_a, const float *d_b, int w, int h, int ch,
+                 float range);
 
 /* ---- noise level of an image (restated in numpy by tests/sigma_ref.py): a block-DCT percentile
  * estimator. HWC image on the 0..255 scale, w, h >= 8, ch >= 1; every channel by itself:
