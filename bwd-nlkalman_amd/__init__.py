@@ -40,6 +40,7 @@ HIP_SYMBOLS = [
     "nlk_sigma_default_params", "nlk_dev_estimate_sigma",
     "nlk_curve_default_params", "nlk_dev_estimate_noise_curve", "nlk_vst_scale", "nlk_dev_vst_forward",
     "nlk_dev_vst_inverse", "nlk_dev_noise_affine",
+    "nlk_yuv_format_from_tag", "nlk_yuv_frame_bytes", "nlk_dev_yuv_to_rgb", "nlk_dev_rgb_to_yuv",
 ]
 API_SYMBOLS = [
     "rgb2opp", "opp2rgb", "warp_bicubic", "nlkalman_default_params",
@@ -82,6 +83,17 @@ class CurveParams(C.Structure):
 
 
 CURVE_BIN = np.dtype([("nblocks", np.int32), ("nsel", np.int32), ("mean", np.float32), ("var", np.float32)])
+
+
+class YuvFormat(C.Structure):
+    """struct nlk_yuv_format (include/nlk_hip.h): a planar Y'CbCr frame's subsampling, chroma siting, sample depth,
+    range and matrix."""
+    _fields_ = [("mono", C.c_int), ("sx", C.c_int), ("sy", C.c_int), ("cosited_x", C.c_int), ("depth", C.c_int),
+                ("full_range", C.c_int), ("matrix", C.c_int)]
+
+    def frame_bytes(self, w, h):
+        """Bytes of one w x h frame (0 if refused)."""
+        return int(hip().nlk_yuv_frame_bytes(int(w), int(h), C.byref(self)))
 
 
 class Timings(C.Structure):
@@ -177,6 +189,11 @@ def hip():
         L.nlk_dev_vst_forward.argtypes = [vp, fp, fp, C.c_size_t, i, vp, f]
         L.nlk_dev_vst_inverse.argtypes = [vp, fp, fp, C.c_size_t, i, vp, f, i]
         L.nlk_dev_noise_affine.argtypes = [vp, fp, fp, C.c_size_t, i, vp, C.c_uint32]
+        L.nlk_yuv_format_from_tag.argtypes = [C.POINTER(YuvFormat), C.c_char_p]
+        L.nlk_yuv_frame_bytes.argtypes = [i, i, C.POINTER(YuvFormat)]
+        L.nlk_yuv_frame_bytes.restype = C.c_size_t
+        L.nlk_dev_yuv_to_rgb.argtypes = [vp, fp, vp, i, i, C.POINTER(YuvFormat)]
+        L.nlk_dev_rgb_to_yuv.argtypes = [vp, vp, fp, i, i, C.POINTER(YuvFormat)]
         L.nlk_host_tables.argtypes = [i, vp, vp, vp]
         L.nlk_ctx_set_deterministic.argtypes = [vp, i]
         L.nlk_ctx_reload_switches.argtypes = [vp]
@@ -252,6 +269,17 @@ def tvl1_params(w, h, **over):
     p.nscales = hip().nlk_tvl1_scales(w, h, p.nscales, p.zfactor)
     p.fscale = min(p.fscale, p.nscales)
     return p
+
+
+def yuv_format_from_tag(tag=None, full_range=False, matrix=709):
+    """nlk_yuv_format_from_tag: the YuvFormat of a YUV4MPEG2 `C` tag value (None or "" = the tag is absent), with the
+    range and matrix the caller chooses. An unsupported tag raises NlkError."""
+    f = YuvFormat()
+    rc = hip().nlk_yuv_format_from_tag(C.byref(f), None if tag is None else str(tag).encode())
+    if rc:
+        raise NlkError(f"rc={rc}: " + hip().nlk_last_error(None).decode())
+    f.full_range, f.matrix = int(bool(full_range)), int(matrix)
+    return f
 
 
 def sigma_params(**over):
@@ -611,6 +639,68 @@ class Context:
         """d_out[i] = d_in[i] + sqrt(max(a_c d_in[i] + b_c, 0)) N_i with awgn's deviates N_i (d_out may be d_in)."""
         a = _ab(ab, ch)
         self._chk(self.L.nlk_dev_noise_affine(self.h, d_out, d_in, n, ch, a.ctypes.data, int(seed) & 0xFFFFFFFF))
+
+    # ---- planar Y'CbCr frames <-> HWC float RGB (include/nlk_hip.h: nlk_dev_yuv_to_rgb / nlk_dev_rgb_to_yuv)
+    def yuv_to_rgb_dev(self, d_rgb, d_yuv, w, h, fmt):
+        """d_rgb (h, w, 3 or 1 for mono; float32, 0..255) = the frame d_yuv (device pointers). Not synchronised."""
+        self._chk(self.L.nlk_dev_yuv_to_rgb(self.h, d_rgb, d_yuv, w, h, C.byref(fmt)))
+
+    def rgb_to_yuv_dev(self, d_yuv, d_rgb, w, h, fmt):
+        """The frame d_yuv (fmt.frame_bytes(w, h) bytes) = the codes of d_rgb (device pointers). Not synchronised."""
+        self._chk(self.L.nlk_dev_rgb_to_yuv(self.h, d_yuv, d_rgb, w, h, C.byref(fmt)))
+
+    def yuv_to_rgb(self, buf, w, h, fmt):
+        """The (h, w, ch) float32 RGB image (ch = 1 for mono) of one frame's payload. buf: a torch tensor on this
+        context's device (any dtype, fmt.frame_bytes(w, h) bytes; a tensor comes back) or a numpy array / bytes
+        (uploaded; a numpy array comes back). Waits for the device."""
+        ch, nbytes = (1 if fmt.mono else 3), fmt.frame_bytes(w, h)
+        if hasattr(buf, "data_ptr"):
+            import torch
+            if buf.numel() * buf.element_size() != nbytes or not buf.is_contiguous():
+                raise ValueError(f"yuv_to_rgb: want a contiguous tensor of {nbytes} bytes")
+            out = torch.empty((h, w, ch), dtype=torch.float32, device=buf.device)
+            torch.cuda.current_stream(buf.device).synchronize()
+            self.yuv_to_rgb_dev(out.data_ptr(), buf.data_ptr(), w, h, fmt)
+            self.sync()
+            return out
+        a = np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray)) else np.ascontiguousarray(buf).view(np.uint8).ravel()
+        if a.nbytes != nbytes:
+            raise ValueError(f"yuv_to_rgb: the payload holds {a.nbytes} bytes, the frame {nbytes}")
+        d_yuv, d_rgb = self.upload(a), self.alloc(w * h * ch * 4)
+        try:
+            self.yuv_to_rgb_dev(d_rgb, d_yuv, w, h, fmt)
+            return self.download(d_rgb, (h, w, ch))
+        finally:
+            self.free(d_yuv)
+            self.free(d_rgb)
+
+    def rgb_to_yuv(self, rgb, fmt):
+        """One frame's payload (uint8 [fmt.frame_bytes(w, h)]; little-endian uint16 samples above 8 bit) from the
+        (h, w, ch) float32 image rgb (ch = 1, or (h, w), for mono): a torch tensor on this context's device gives a
+        tensor, a numpy array an array. Waits for the device."""
+        ch = 1 if fmt.mono else 3
+        if hasattr(rgb, "data_ptr"):
+            import torch
+            h, w = int(rgb.shape[0]), int(rgb.shape[1])
+            if rgb.dtype != torch.float32 or rgb.numel() != w * h * ch or not rgb.is_contiguous():
+                raise ValueError(f"rgb_to_yuv: want a contiguous float32 tensor (h, w, {ch})")
+            out = torch.empty((fmt.frame_bytes(w, h),), dtype=torch.uint8, device=rgb.device)
+            torch.cuda.current_stream(rgb.device).synchronize()
+            self.rgb_to_yuv_dev(out.data_ptr(), rgb.data_ptr(), w, h, fmt)
+            self.sync()
+            return out
+        a = _img(rgb)
+        h, w = a.shape[:2]
+        if a.shape[2] != ch:
+            raise ValueError(f"rgb_to_yuv: the image has {a.shape[2]} channels, the format {ch}")
+        nbytes = fmt.frame_bytes(w, h)
+        d_rgb, d_yuv = self.upload(a), self.alloc(max(nbytes, 1))
+        try:
+            self.rgb_to_yuv_dev(d_yuv, d_rgb, w, h, fmt)
+            return self.download(d_yuv, (nbytes,), np.uint8)
+        finally:
+            self.free(d_rgb)
+            self.free(d_yuv)
 
     def frame_accumulate(self, d_acc, d_cur, d_prev, d_basic, w, h, ch, sigma, params, oy,
                          ngy, smoother=False):

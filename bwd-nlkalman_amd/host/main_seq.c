@@ -71,6 +71,7 @@
 #include "imgio.h"
 #include "nlk_hip.h"
 #include "nlkalman.h"
+#include "seq_step.h"
 
 #ifndef NLK_SEQ_GT
 #define NLK_SEQ_GT 0
@@ -87,26 +88,6 @@ static nlk_ctx *C;
       exit(1);                                                       \
     }                                                                \
   } while (0)
-
-static void unset(struct nlkalman_params *p) {
-  p->patch_sz = p->search_sz_x = p->search_sz_t = -1;
-  p->npatches_x = p->npatches_t = p->npatches_tagg = -1;
-  p->dista_lambda = p->beta_x = p->beta_t = -1.f;
-}
-
-/* "a b  c" -> argv {prog, a, b, c}; returns argc */
-static int split(const char *prog, const char *s, const char ***argv_out) {
-  char *buf = strdup(s ? s : "");
-  int n = 1, cap = 64;
-  const char **av = malloc(sizeof(char *) * cap);
-  av[0] = prog;
-  for (char *t = strtok(buf, " \t\n"); t; t = strtok(NULL, " \t\n")) {
-    if (n + 1 >= cap) av = realloc(av, sizeof(char *) * (cap *= 2));
-    av[n++] = t;
-  }
-  *argv_out = av;
-  return n;
-}
 
 /* ---- write-behind: a bounded queue of (path, array) jobs served by worker threads. The arrays
  * are page-locked buffers of one frame each, recycled through a pool: downloads run at the
@@ -433,29 +414,8 @@ int main(int argc, const char **argv) {
 
   /* filter / smoother parameters: the options of nlkalman-flt and nlkalman-smo, same grammar */
   struct nlkalman_params f1, f2, s1;
-  unset(&f1); unset(&f2); unset(&s1);
+  seq_unset_params(&f1); seq_unset_params(&f2); seq_unset_params(&s1);
   int verbose = 0;
-  const struct cli_option fopts[] = {
-      {CLI_INT, 0, "f1_p", &f1.patch_sz, "patch size"},
-      {CLI_INT, 0, "f1_sx", &f1.search_sz_x, "search radius (spatial filtering)"},
-      {CLI_INT, 0, "f1_st", &f1.search_sz_t, "search radius (temporal filtering)"},
-      {CLI_INT, 0, "f1_nx", &f1.npatches_x, "number of similar patches spatial"},
-      {CLI_INT, 0, "f1_nt", &f1.npatches_t, "number of similar patches kalman"},
-      {CLI_INT, 0, "f1_nt_agg", &f1.npatches_tagg, "number of similar patches kalman spatial average"},
-      {CLI_FLOAT, 0, "f1_bx", &f1.beta_x, "noise multiplier in spatial filtering"},
-      {CLI_FLOAT, 0, "f1_bt", &f1.beta_t, "noise multiplier in kalman filtering"},
-      {CLI_FLOAT, 0, "f1_l", &f1.dista_lambda, "noisy patch weight in patch distance"},
-      {CLI_INT, 0, "f2_p", &f2.patch_sz, "patch size"},
-      {CLI_INT, 0, "f2_sx", &f2.search_sz_x, "search radius (spatial filtering)"},
-      {CLI_INT, 0, "f2_st", &f2.search_sz_t, "search radius (temporal filtering)"},
-      {CLI_INT, 0, "f2_nx", &f2.npatches_x, "number of similar patches spatial"},
-      {CLI_INT, 0, "f2_nt", &f2.npatches_t, "number of similar patches kalman"},
-      {CLI_INT, 0, "f2_nt_agg", &f2.npatches_tagg, "number of similar patches kalman spatial average"},
-      {CLI_FLOAT, 0, "f2_bx", &f2.beta_x, "noise multiplier in spatial filtering"},
-      {CLI_FLOAT, 0, "f2_bt", &f2.beta_t, "noise multiplier in kalman filtering"},
-      {CLI_FLOAT, 0, "f2_l", &f2.dista_lambda, "noisy patch weight in patch distance"},
-      {CLI_INT, 'v', "verbose", &verbose, "verbose output"},
-      {CLI_END, 0, NULL, NULL, NULL}};
   const struct cli_option sopts[] = {
       {CLI_INT, 0, "s1_p", &s1.patch_sz, "patch size"},
       {CLI_INT, 0, "s1_st", &s1.search_sz_t, "search region radius"},
@@ -465,11 +425,10 @@ int main(int argc, const char **argv) {
       {CLI_FLOAT, 0, "s1_l", &s1.dista_lambda, "noisy patch weight in patch distance"},
       {CLI_INT, 'v', "verbose", &verbose, "verbose output"},
       {CLI_END, 0, NULL, NULL, NULL}};
-  const char **av;
-  int ac = split("nlkalman-seq (FPM)", fpm, &av);
-  cli_parse(fopts, "nlkalman-seq (FPM)", "filtering parameters", ac, av);
+  seq_parse_fpm("nlkalman-seq (FPM)", fpm, &f1, &f2, &verbose);
   if (smoothing) {
-    ac = split("nlkalman-seq (SPM)", spm, &av);
+    const char **av;
+    const int ac = seq_split("nlkalman-seq (SPM)", spm, &av);
     cli_parse(sopts, "nlkalman-seq (SPM)", "smoothing parameters", ac, av);
   }
   if (f1.patch_sz == 0 || f2.patch_sz == 0) {
@@ -626,29 +585,12 @@ int main(int argc, const char **argv) {
       nlkalman_default_params(&f2, sigma, FLT2);
       nlkalman_default_params(&s1, sigma, SMO1);
     }
-    if (vst) CHK(nlk_dev_vst_forward(C, d_rgb, d_rgb, (size_t)w * h * ch, ch, vst_ab, vst_s));
-    CHK(nlk_d2d(C, d_noisy, d_rgb, bytes));
-    CHK(nlk_dev_rgb2opp(C, d_noisy, w, h, ch));
     float *n1 = dev_frame(bytes), *n2 = dev_frame(bytes);
-    if (t == 0) {
-      CHK(nlk_dev_filter_frame(C, n1, d_noisy, NULL, NULL, w, h, ch, sigma, &f1));
-      CHK(nlk_dev_filter_frame(C, n2, d_noisy, NULL, n1, w, h, ch, sigma, &f2));
-    } else {
-      /* backward flow noisy_t -> flt2_{t-1}, occlusion mask (script lines 57-73) */
-      nlk_tvl1_default_params(&of);
-      of.lambda = dw1; of.fscale = fs1;
-      of.nscales = nlk_tvl1_scales(w, h, of.nscales, of.zfactor);
-      if (of.nscales < of.fscale) of.fscale = of.nscales;
-      CHK(nlk_dev_gray(C, d_g0, d_rgb, w, h, ch));
-      CHK(nlk_d2d(C, d_tmp, flt2[t - 1], bytes));
-      CHK(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
-      CHK(nlk_dev_gray(C, d_g1, d_tmp, w, h, ch));
-      CHK(nlk_dev_tvl1_flow(C, d_flow, d_g0, d_g1, w, h, &of, NULL));
-      CHK(nlk_dev_occlusion_mask(C, d_occ, d_flow, w, h, th1));
-      CHK(nlk_dev_warp_bicubic(C, d_warp, flt1, d_flow, d_occ, w, h, ch));
-      CHK(nlk_dev_filter_frame(C, n1, d_noisy, d_warp, NULL, w, h, ch, sigma, &f1));
-      CHK(nlk_dev_warp_bicubic(C, d_warp, flt2[t - 1], d_flow, d_occ, w, h, ch));
-      CHK(nlk_dev_filter_frame(C, n2, d_noisy, d_warp, n1, w, h, ch, sigma, &f2));
+    const struct seq_step step = {C, w, h, ch, sigma, &f1, &f2, vst ? vst_ab : NULL, vst_s, fs1, dw1, th1, d_rgb,
+                                  d_noisy, d_tmp, d_warp, d_g0, d_g1, d_occ, d_flow, t ? flt1 : NULL,
+                                  t ? flt2[t - 1] : NULL, n1, n2};
+    CHK(seq_forward_step(&step));
+    if (t > 0) { /* the flow and its mask (script lines 57-73) */
       write_dev(path_of(out, "bflo1-%03d.flo", i), d_flow, w, h, 2);
       write_dev(path_of(out, "bocc1-%03d.png", i), d_occ, w, h, 1);
     }

@@ -1,0 +1,367 @@
+/* main_y4m.c — `nlkalman-y4m`: the forward recursion of nlkalman-seq on a YUV4MPEG2 stream, as decoders pipe it:
+ *
+ *   ffmpeg -i in.mkv -f yuv4mpegpipe -strict -1 - | nlkalman-y4m 20 | ffmpeg -i - out.mkv
+ *
+ *   nlkalman-y4m [options] SIG [IN [OUT]]      IN, OUT: a file or "-" (default: stdin, stdout)
+ *     SIG            a number | auto | vst | vst:A,B       (nlkalman-seq's forms and meaning, host/main_seq.c)
+ *     --matrix 601|709|auto    auto (default): 709 when W >= 1280 or H > 576, else 601
+ *     --range limited|full|auto   auto (default): the header's XCOLORRANGE, else limited
+ *     --fpm "..."    nlkalman-flt options, as nlkalman-seq's FPM
+ *     --opm "FSCALE DW TH"   flow parameters of the backward pass (default "1 0.25 0.75")
+ *     --frames N     stop after N frames
+ *     --copy         convert to RGB and back only (no filter): the conversion path by itself
+ *     --probe        no GPU, no output stream: parse IN, print one line
+ *                    "W H FN:FD I A C depth range matrix frames" and exit (counts the frames, checks every payload)
+ *     -v             one line per frame on stderr
+ *
+ * Per frame: payload -> pinned buffer -> nlk_h2d -> nlk_dev_yuv_to_rgb -> the forward step of nlkalman-seq
+ * (host/seq_step.c) -> nlk_dev_opp2rgb on a copy of flt2 -> the inverse transform under SIG = vst ->
+ * nlk_dev_rgb_to_yuv -> nlk_d2h -> the writer. The colour conversion runs on the GPU in both directions, so a 1080p
+ * 4:2:0 8-bit frame crosses the link as 3.1 MB each way and the host encodes nothing. The output is the flt2 frames
+ * in the input's format under the input's header line. Only flt1 and flt2 of the previous frame stay resident:
+ * memory does not grow with the stream. There is no smoother (it runs backwards over a whole sequence).
+ *
+ * A reader thread and a writer thread work beside the GPU on a ring of pinned payload buffers: frame t + 1 is read
+ * while frame t is filtered and frame t - 1 is written. The two copies across the link (nlk_h2d, nlk_d2h: 3 MB each,
+ * ~0.1 ms) are synchronous on the main thread, so the GPU waits for them: a known limit. NLK_SEQ_IO_THREADS=0, or a ring that cannot be allocated,
+ * gives in-line I/O on one pageable buffer.
+ *
+ * Every diagnostic goes to stderr (stdout may be the stream), the "sigma ..." and "vst ..." lines of SIG = auto | vst
+ * included. Exit status 0, or 1 on any error; a stream that ends inside a frame gives 1 after every complete frame
+ * before it has been filtered and written. */
+#include <math.h>
+#include <pthread.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "nlk_hip.h"
+#include "nlkalman.h"
+#include "seq_step.h"
+#include "y4m.h"
+
+#define PROG "nlkalman-y4m"
+
+nlk_ctx *nlkalman_hip_context(void); /* libnlkalman.so: the process-wide device context */
+
+static nlk_ctx *C;
+#define CHK(call)                                             \
+  do {                                                        \
+    if ((call) != NLK_OK) {                                   \
+      fprintf(stderr, "%s: %s\n", PROG, nlk_last_error(C));   \
+      return 1;                                               \
+    }                                                         \
+  } while (0)
+
+/* ---- the ring: slot i holds frame i, i + RING, ...; a slot goes FREE -> (reader) INPUT -> (main) OUTPUT -> (writer)
+ * FREE, and every party walks the slots in order. INPUT_END / OUTPUT_END in place of a frame end the stream. */
+#define RING 4
+enum { FREE, INPUT, INPUT_END, OUTPUT, OUTPUT_END };
+static struct {
+  pthread_mutex_t mu;
+  pthread_cond_t cv;
+  int state[RING];
+  void *buf[RING];
+  int threads;         /* 0: in-line I/O on buf[0] */
+  FILE *in, *out;
+  const struct y4m_header *hd;
+  long max_frames;     /* < 0: no limit */
+  int read_failed, write_failed;
+  char read_err[Y4M_ERR_MAX], write_err[Y4M_ERR_MAX];
+} G = {PTHREAD_MUTEX_INITIALIZER, PTHREAD_COND_INITIALIZER, {0}, {0}, 0, NULL, NULL, NULL, -1, 0, 0, "", ""};
+
+static void slot_wait(int i, int s1, int s2) {
+  pthread_mutex_lock(&G.mu);
+  while (G.state[i] != s1 && G.state[i] != s2) pthread_cond_wait(&G.cv, &G.mu);
+  pthread_mutex_unlock(&G.mu);
+}
+static void slot_set(int i, int s) {
+  pthread_mutex_lock(&G.mu);
+  G.state[i] = s;
+  pthread_cond_broadcast(&G.cv);
+  pthread_mutex_unlock(&G.mu);
+}
+
+/* 1 = a frame in buf, 0 = the stream is over (G.read_failed says how) */
+static int read_one(void *buf, long done) {
+  if (G.max_frames >= 0 && done >= G.max_frames) return 0;
+  const int r = y4m_read_frame(G.in, G.hd, buf, G.read_err);
+  if (r < 0) G.read_failed = 1;
+  return r == 1;
+}
+/* (the flag is the writer thread's to set and the main thread's to read: under the lock) */
+static int write_has_failed(void) {
+  pthread_mutex_lock(&G.mu);
+  const int v = G.write_failed;
+  pthread_mutex_unlock(&G.mu);
+  return v;
+}
+static void write_one(const void *buf) {
+  if (write_has_failed() || !y4m_write_frame(G.out, G.hd, buf, G.write_err)) return;
+  pthread_mutex_lock(&G.mu);
+  G.write_failed = 1;
+  pthread_mutex_unlock(&G.mu);
+}
+
+static void *reader(void *arg) {
+  (void)arg;
+  for (long t = 0;; ++t) {
+    const int i = (int)(t % RING);
+    slot_wait(i, FREE, FREE);
+    const int got = read_one(G.buf[i], t);
+    slot_set(i, got ? INPUT : INPUT_END);
+    if (!got) return NULL;
+  }
+}
+static void *writer(void *arg) {
+  (void)arg;
+  for (long t = 0;; ++t) {
+    const int i = (int)(t % RING);
+    slot_wait(i, OUTPUT, OUTPUT_END);
+    if (G.state[i] == OUTPUT_END) return NULL;
+    write_one(G.buf[i]);
+    slot_set(i, FREE);
+  }
+}
+
+/* the next input frame: its buffer, or NULL at the end of the stream */
+static void *frame_get(long t) {
+  if (!G.threads) return read_one(G.buf[0], t) ? G.buf[0] : NULL;
+  const int i = (int)(t % RING);
+  slot_wait(i, INPUT, INPUT_END);
+  return G.state[i] == INPUT ? G.buf[i] : NULL;
+}
+/* the same buffer, now holding the output frame */
+static void frame_put(long t) {
+  if (!G.threads) write_one(G.buf[0]);
+  else slot_set((int)(t % RING), OUTPUT);
+}
+
+static int probe(FILE *in, const struct y4m_header *hd, const char *range, int matrix, long max_frames) {
+  char err[Y4M_ERR_MAX];
+  void *buf = malloc(hd->frame_bytes);
+  if (!buf) { fprintf(stderr, "%s: out of memory (%zu bytes)\n", PROG, hd->frame_bytes); return 1; }
+  long n = 0;
+  int r = 0;
+  while ((max_frames < 0 || n < max_frames) && (r = y4m_read_frame(in, hd, buf, err)) == 1) ++n;
+  free(buf);
+  if (r < 0) { fprintf(stderr, "%s: frame %ld: %s\n", PROG, n + 1, err); return 1; }
+  printf("%d %d %d:%d %c %d:%d %s %d %s %d %ld\n", hd->w, hd->h, hd->fps_n, hd->fps_d, hd->interlace, hd->asp_n,
+         hd->asp_d, hd->ctag[0] ? hd->ctag : "420jpeg", hd->fmt.depth, range, matrix, n);
+  return 0;
+}
+
+static int usage(void) {
+  fprintf(stderr,
+          "usage: %s [options] SIG [IN [OUT]]     IN, OUT: a file or \"-\" (default: stdin, stdout)\n"
+          "  SIG: a number | auto | vst | vst:A,B\n"
+          "  --matrix 601|709|auto  --range limited|full|auto  --fpm \"...\"  --opm \"FSCALE DW TH\"\n"
+          "  --frames N  --copy  --probe  -v       (see the header of main_y4m.c)\n", PROG);
+  return 1;
+}
+
+int main(int argc, const char **argv) {
+  const char *matrix_s = "auto", *range_s = "auto", *fpm = "", *opm = "1 0.25 0.75", *pos[3] = {NULL, NULL, NULL};
+  long max_frames = -1;
+  int copy = 0, want_probe = 0, verbose = 0, npos = 0;
+  for (int i = 1; i < argc; ++i) {
+    const char *a = argv[i];
+    const char **val = NULL;
+    if (!strcmp(a, "--matrix")) val = &matrix_s;
+    else if (!strcmp(a, "--range")) val = &range_s;
+    else if (!strcmp(a, "--fpm")) val = &fpm;
+    else if (!strcmp(a, "--opm")) val = &opm;
+    if (val) {
+      if (++i >= argc) { fprintf(stderr, "%s: %s needs a value\n", PROG, a); return 1; }
+      *val = argv[i];
+    } else if (!strcmp(a, "--frames")) {
+      char *e;
+      if (++i >= argc || (max_frames = strtol(argv[i], &e, 10)) < 0 || *e || e == argv[i]) {
+        fprintf(stderr, "%s: --frames needs a count >= 0\n", PROG);
+        return 1;
+      }
+    } else if (!strcmp(a, "--copy")) copy = 1;
+    else if (!strcmp(a, "--probe")) want_probe = 1;
+    else if (!strcmp(a, "-v")) verbose = 1;
+    else if (!strcmp(a, "-h") || !strcmp(a, "--help")) { usage(); return 0; }
+    else if (a[0] == '-' && a[1] && !(npos == 0 && (a[1] == '.' || (a[1] >= '0' && a[1] <= '9')))) {
+      fprintf(stderr, "%s: unknown option %s\n", PROG, a);
+      return usage();
+    } else if (npos < 3) pos[npos++] = a;
+    else return usage();
+  }
+  if (npos < 1) return usage();
+  const char *sig = pos[0];
+
+  /* SIG, as nlkalman-seq reads it */
+  const int vst = !strncmp(sig, "vst", 3);
+  float vst_a = 0.f, vst_b = 0.f;
+  if (vst && sig[3] && (sscanf(sig + 3, ":%f,%f", &vst_a, &vst_b) != 2 || !(vst_a >= 0.f) || !(vst_b >= 0.f) ||
+                        !(vst_a + vst_b > 0.f) || !(vst_a + vst_b <= 3e38f))) {
+    fprintf(stderr, "%s: SIG = %s: want vst or vst:A,B with A, B >= 0, not both 0\n", PROG, sig);
+    return 1;
+  }
+  const int vst_given = vst && sig[3];
+  const int auto_sigma = vst || !strcmp(sig, "auto");
+  float sigma = auto_sigma ? 0.f : atof(sig);
+  int fs = 1;
+  float dw = 0.25f, th = 0.75f;
+  if (sscanf(opm, "%d %f %f", &fs, &dw, &th) != 3) {
+    fprintf(stderr, "%s: --opm must hold 3 numbers: FSCALE DW TH\n", PROG);
+    return 1;
+  }
+  int matrix = 0, range = -1;
+  if (!strcmp(matrix_s, "601")) matrix = 601;
+  else if (!strcmp(matrix_s, "709")) matrix = 709;
+  else if (strcmp(matrix_s, "auto")) { fprintf(stderr, "%s: --matrix %s: want 601, 709 or auto\n", PROG, matrix_s); return 1; }
+  if (!strcmp(range_s, "limited")) range = 0;
+  else if (!strcmp(range_s, "full")) range = 1;
+  else if (strcmp(range_s, "auto")) { fprintf(stderr, "%s: --range %s: want limited, full or auto\n", PROG, range_s); return 1; }
+  struct nlkalman_params f1, f2;
+  seq_unset_params(&f1); seq_unset_params(&f2);
+  seq_parse_fpm(PROG " (--fpm)", fpm, &f1, &f2, &verbose);
+  if (f1.patch_sz == 0 || f2.patch_sz == 0) {
+    fprintf(stderr, "%s: both filtering iterations are needed (f1_p, f2_p != 0)\n", PROG);
+    return 1;
+  }
+
+  FILE *in = !pos[1] || !strcmp(pos[1], "-") ? stdin : fopen(pos[1], "rb");
+  if (!in) { fprintf(stderr, "%s: cannot open %s\n", PROG, pos[1]); return 1; }
+  struct y4m_header hd;
+  char err[Y4M_ERR_MAX];
+  if (y4m_read_header(in, &hd, err)) { fprintf(stderr, "%s: %s\n", PROG, err); return 1; }
+  if (!matrix) matrix = hd.w >= 1280 || hd.h > 576 ? 709 : 601;
+  if (range < 0) range = hd.range == 1;
+  hd.fmt.matrix = matrix;
+  hd.fmt.full_range = range;
+  if (want_probe) return probe(in, &hd, range ? "full" : "limited", matrix, max_frames);
+
+  FILE *out = !pos[2] || !strcmp(pos[2], "-") ? stdout : fopen(pos[2], "wb");
+  if (!out) { fprintf(stderr, "%s: cannot open %s\n", PROG, pos[2]); return 1; }
+  if (y4m_write_header(out, &hd, err)) { fprintf(stderr, "%s: %s\n", PROG, err); return 1; }
+
+  const int w = hd.w, h = hd.h, ch = hd.fmt.mono ? 1 : 3;
+  if ((double)w * h * ch * sizeof(float) > 2e9) { /* (the frame calls index with int) */
+    fprintf(stderr, "%s: a %d x %d frame is too large for the filter\n", PROG, w, h);
+    return 1;
+  }
+  const size_t bytes = (size_t)w * h * ch * sizeof(float), npix = (size_t)w * h;
+  C = nlkalman_hip_context();
+
+  /* the ring (pinned), or one pageable buffer */
+  G.in = in; G.out = out; G.hd = &hd; G.max_frames = max_frames;
+  const char *e = getenv("NLK_SEQ_IO_THREADS");
+  G.threads = !(e && atoi(e) == 0);
+  if (G.threads) {
+    int n = 0;
+    for (; n < RING; ++n)
+      if (nlk_host_alloc(C, &G.buf[n], hd.frame_bytes) != NLK_OK) break;
+    if (n < RING) { /* not the whole ring: in-line I/O */
+      while (n > 0) nlk_host_free(C, G.buf[--n]);
+      G.threads = 0;
+    }
+  }
+  if (!G.threads && !(G.buf[0] = malloc(hd.frame_bytes))) {
+    fprintf(stderr, "%s: out of memory (%zu bytes)\n", PROG, hd.frame_bytes);
+    return 1;
+  }
+  pthread_t th_r, th_w;
+  if (G.threads && pthread_create(&th_r, NULL, reader, NULL)) G.threads = 0;
+  if (G.threads && pthread_create(&th_w, NULL, writer, NULL)) {
+    fprintf(stderr, "%s: cannot start the writer thread\n", PROG);
+    return 1;
+  }
+
+  enum { NDEV = 13 };
+  void *dp[NDEV] = {0};
+  const size_t want[NDEV] = {hd.frame_bytes, bytes, bytes, bytes, bytes, npix * 4, npix * 4, npix * 4, npix * 8,
+                             bytes, bytes, bytes, bytes};
+  for (int i = 0; i < NDEV; ++i) CHK(nlk_dev_alloc(C, &dp[i], want[i]));
+  void *d_yuv = dp[0];
+  float *d_rgb = dp[1], *d_noisy = dp[2], *d_tmp = dp[3], *d_warp = dp[4], *d_g0 = dp[5], *d_g1 = dp[6], *d_occ = dp[7],
+        *d_flow = dp[8];
+  float *flt1[2] = {dp[9], dp[10]}, *flt2[2] = {dp[11], dp[12]}; /* this frame's and the previous one's, by turns */
+  float *vst_ab = NULL, vst_s = 0.f;
+  if (!auto_sigma) {
+    nlkalman_default_params(&f1, sigma, FLT1);
+    nlkalman_default_params(&f2, sigma, FLT2);
+  }
+
+  long t = 0;
+  int failed = 0;
+  for (;; ++t) {
+    void *buf = frame_get(t);
+    if (!buf) break;
+    CHK(nlk_h2d(C, d_yuv, buf, hd.frame_bytes));
+    CHK(nlk_dev_yuv_to_rgb(C, d_rgb, d_yuv, w, h, &hd.fmt));
+    const float *d_out = d_rgb;
+    if (!copy) {
+      if (vst && t == 0) { /* the noise curve of the first frame, the scale of its transform = the sigma of the run */
+        vst_ab = malloc(sizeof(float) * 2 * ch);
+        if (vst_given) {
+          for (int c = 0; c < ch; ++c) { vst_ab[2 * c] = vst_a; vst_ab[2 * c + 1] = vst_b; }
+        } else {
+          void *d_curve = NULL;
+          CHK(nlk_dev_alloc(C, &d_curve, sizeof(float) * 2 * ch));
+          CHK(nlk_dev_estimate_noise_curve(C, d_curve, NULL, d_rgb, w, h, ch, NULL));
+          CHK(nlk_d2h(C, vst_ab, d_curve, sizeof(float) * 2 * ch));
+          nlk_dev_free(C, d_curve);
+        }
+        sigma = vst_s = nlk_vst_scale(vst_ab, ch);
+        if (!(sigma > 0.f)) {
+          fprintf(stderr, "%s: SIG = vst: the first frame gives no noise curve (a_0 = %g, b_0 = %g)\n", PROG,
+                  (double)vst_ab[0], (double)vst_ab[1]);
+          failed = 1;
+          break;
+        }
+        fprintf(stderr, "vst");
+        for (int c = 0; c < 2 * ch; ++c) fprintf(stderr, " %.9g", (double)vst_ab[c]);
+        fprintf(stderr, " sigma %.9g\n", (double)sigma);
+      } else if (auto_sigma && t == 0) { /* the noise level of the first frame */
+        void *d_sigma = NULL;
+        CHK(nlk_dev_alloc(C, &d_sigma, sizeof(float) * (1 + ch)));
+        CHK(nlk_dev_estimate_sigma(C, d_sigma, NULL, d_rgb, w, h, ch, NULL));
+        CHK(nlk_d2h(C, &sigma, d_sigma, sizeof(float)));
+        nlk_dev_free(C, d_sigma);
+        if (!(sigma > 0.f)) {
+          fprintf(stderr, "%s: SIG = auto: the first frame gives sigma = %g\n", PROG, (double)sigma);
+          failed = 1;
+          break;
+        }
+        fprintf(stderr, "sigma %.9g\n", (double)sigma);
+      }
+      if (auto_sigma && t == 0) {
+        nlkalman_default_params(&f1, sigma, FLT1);
+        nlkalman_default_params(&f2, sigma, FLT2);
+      }
+      const int cur = (int)(t & 1), prv = cur ^ 1;
+      const struct seq_step step = {C, w, h, ch, sigma, &f1, &f2, vst_ab, vst_s, fs, dw, th, d_rgb, d_noisy, d_tmp,
+                                    d_warp, d_g0, d_g1, d_occ, d_flow, t ? flt1[prv] : NULL, t ? flt2[prv] : NULL,
+                                    flt1[cur], flt2[cur]};
+      CHK(seq_forward_step(&step));
+      CHK(nlk_d2d(C, d_tmp, flt2[cur], bytes));
+      CHK(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
+      if (vst_ab) CHK(nlk_dev_vst_inverse(C, d_tmp, d_tmp, npix * ch, ch, vst_ab, vst_s, 1));
+      d_out = d_tmp;
+    }
+    CHK(nlk_dev_rgb_to_yuv(C, d_yuv, d_out, w, h, &hd.fmt));
+    CHK(nlk_d2h(C, buf, d_yuv, hd.frame_bytes));
+    frame_put(t);
+    if (verbose) fprintf(stderr, "frame %ld %s\n", t + 1, copy ? "converted" : "filtered");
+    if (write_has_failed()) { /* nobody reads the output any more: stop filtering (the process ends, threads and all) */
+      fprintf(stderr, "%s: %s\n", PROG, G.write_err);
+      return 1;
+    }
+  }
+  if (G.threads) {
+    slot_set((int)(t % RING), OUTPUT_END); /* (slot t is the main thread's: it holds the end mark or a frame not used) */
+    pthread_join(th_w, NULL);
+    /* after an early `break` the reader may still wait for a slot: the process ends without joining it */
+  }
+  if (fflush(out) || (out != stdout && fclose(out))) { fprintf(stderr, "%s: write error\n", PROG); failed = 1; }
+  if (G.write_failed) { fprintf(stderr, "%s: %s\n", PROG, G.write_err); failed = 1; }
+  if (G.read_failed) { fprintf(stderr, "%s: frame %ld: %s\n", PROG, t + 1, G.read_err); failed = 1; }
+  for (int i = 0; i < NDEV; ++i) nlk_dev_free(C, dp[i]);
+  return failed;
+}

@@ -38,6 +38,8 @@
  *   nlk_dev_estimate_noise_curve, nlk_dev_vst_forward / _inverse, nlk_dev_noise_affine
  *                                       nothing: the reference knows white noise only
  *   nlk_dev_ssim                        nothing: the reference measures the squared error only
+ *   nlk_dev_yuv_to_rgb / nlk_dev_rgb_to_yuv, nlk_yuv_format_from_tag, nlk_yuv_frame_bytes
+ *                                       nothing: the reference reads and writes RGB image files only
  */
 #ifndef NLK_HIP_H
 #define NLK_HIP_H
@@ -319,6 +321,39 @@ int nlk_dev_vst_inverse(nlk_ctx *ctx, float *out, const float *in, size_t n, int
  * (host array, finite values, ch in 1..16). out may be in. */
 int nlk_dev_noise_affine(nlk_ctx *ctx, float *out, const float *in, size_t n, int ch, const float *ab,
                          uint32_t seed);
+
+/* ---- planar Y'CbCr frames as decoders deliver them (the payload of a YUV4MPEG2 frame) <-> the HWC float RGB image
+ * of everything above, on the device (restated in numpy by tests/yuv_ref.py).
+ * A frame is the Y plane (w x h samples), then Cb, then Cr (each cw x chh, cw = (w + sx - 1) / sx,
+ * chh = (h + sy - 1) / sy), tightly packed: no row padding, plane starts at any byte (17 x 5 at 8 bit: Cb at byte 85).
+ * Samples are bytes at depth 8 and little-endian uint16 above. */
+struct nlk_yuv_format {
+  int mono;        /* 1: luma only (ch = 1); the chroma fields are ignored */
+  int sx, sy;      /* chroma subsampling per axis, 1 or 2 */
+  int cosited_x;   /* horizontal chroma siting when sx == 2: 0 = centred between luma 2i and 2i+1 (420jpeg),
+                      1 = on luma 2i (420mpeg2, 422). Vertical siting is always centred when sy == 2 */
+  int depth;       /* bits per sample, 8..16; > 8: little-endian uint16 samples */
+  int full_range;  /* 0 = limited (16..235 / 16..240 scaled by 2^(depth-8)), 1 = full */
+  int matrix;      /* 601 or 709 */
+};
+/* host only. The format of a YUV4MPEG2 `C` tag value (NULL or "" when the tag is absent): absent, 420jpeg = 4:2:0
+ * centred; 420mpeg2, 420, 420pN = 4:2:0 co-sited; 422, 422pN = 4:2:2 co-sited; 444, 444pN; mono, monoN (N = 9..16).
+ * full_range = 0 and matrix = 709: the caller overrides both. Anything else (420paldv, 411, 444alpha, ...):
+ * NLK_EUNSUP. */
+int nlk_yuv_format_from_tag(struct nlk_yuv_format *f, const char *ctag);
+/* host only. Bytes of one frame; 0 for a size < 1, a format field out of range or a size that overflows */
+size_t nlk_yuv_frame_bytes(int w, int h, const struct nlk_yuv_format *f);
+/* d_rgb: HWC float32 on the 0..255 scale, ch = 3 (ch = 1 for mono: the luma); d_yuv: a frame as above. Float32
+ * arithmetic in the order DESIGN.md §9 writes out, without contraction: the same input gives the same bits, and
+ * the numpy restatement gives them too. to_rgb interpolates the chroma (centred axis: 3/4, 1/4 of the two nearest
+ * samples; co-sited: the sample or the mean of two; indices clamped) and does not clamp the result; to_yuv decimates
+ * it (centred: the mean of two; co-sited: 1/4, 1/2, 1/4) and rounds to nearest even, clamped to 0 .. 2^depth - 1 (NaN
+ * gives code 0). At 4:4:4 codes -> RGB -> codes is the identity. One pass each, no scratch, no atomics, any w >= 1 and
+ * 1 <= h <= 524280 (8 rows per workgroup, 65535 workgroups along y in one launch; more rows: NLK_EUNSUP);
+ * asynchronous on the context's stream. NLK_EINVAL for a NULL pointer, a non-positive size or a format field outside
+ * the ranges above; the context keeps working after a refused call. */
+int nlk_dev_yuv_to_rgb(nlk_ctx *ctx, float *d_rgb, const void *d_yuv, int w, int h, const struct nlk_yuv_format *f);
+int nlk_dev_rgb_to_yuv(nlk_ctx *ctx, void *d_yuv, const float *d_rgb, int w, int h, const struct nlk_yuv_format *f);
 
 /* Row-strip form used by the multi-GPU driver. The images are a strip of the
  * frame (h rows) that already contains the search halo; targets are the patch
