@@ -41,6 +41,7 @@ HIP_SYMBOLS = [
     "nlk_curve_default_params", "nlk_dev_estimate_noise_curve", "nlk_vst_scale", "nlk_dev_vst_forward",
     "nlk_dev_vst_inverse", "nlk_dev_noise_affine",
     "nlk_yuv_format_from_tag", "nlk_yuv_frame_bytes", "nlk_dev_yuv_to_rgb", "nlk_dev_rgb_to_yuv",
+    "nlk_dev_flow_invert",
 ]
 API_SYMBOLS = [
     "rgb2opp", "opp2rgb", "warp_bicubic", "nlkalman_default_params",
@@ -170,6 +171,7 @@ def hip():
         L.nlk_dev_tvl1_flow.argtypes = [vp, fp, fp, fp, i, i, C.POINTER(Tvl1Params), C.POINTER(i)]
         L.nlk_dev_gray.argtypes = [vp, fp, fp, i, i, i]
         L.nlk_dev_occlusion_mask.argtypes = [vp, fp, fp, i, i, f]
+        L.nlk_dev_flow_invert.argtypes = [vp, fp, fp, i, i, i]
         L.nlk_dev_image_dct.argtypes = [vp, fp, i, i, i, i]
         L.nlk_dev_copy_block.argtypes = [vp, fp, i, fp, i, i, i, i]
         L.nlk_dev_lz3_down.argtypes = [vp, fp, fp, i, i, i]
@@ -500,6 +502,10 @@ class Context:
 
     def occlusion_mask(self, d_mask, d_flow, w, h, th):
         self._chk(self.L.nlk_dev_occlusion_mask(self.h, d_mask, d_flow, w, h, float(th)))
+
+    def flow_invert(self, d_inv, d_flow, w, h, iters=4):
+        """The inverse of a flow by `iters` fixed-point steps (nlk_dev_flow_invert; tests/flowinv_ref.py restates it)."""
+        self._chk(self.L.nlk_dev_flow_invert(self.h, d_inv, d_flow, w, h, int(iters)))
 
     def image_dct(self, d_img, w, h, ch, inverse=False):
         self._chk(self.L.nlk_dev_image_dct(self.h, d_img, w, h, ch, int(inverse)))

@@ -57,7 +57,18 @@
  * downloaded at the end) and written as 8-bit flt1- / flt2- / smo1-%03d.png, the script's final
  * state; OUT/measures gets the script's lines with its plambda arithmetic (write_measures), and stdout
  * one line, the total MSEs as `printf "%f %f %f\n"`. With SIG = auto the noise level is measured on the first
- * NOISY frame, and there is no sigma to make noise with: every OUT/%03d.tif must exist then. */
+ * NOISY frame, and there is no sigma to make noise with: every OUT/%03d.tif must exist then.
+ *
+ * Built with NLK_SEQ_LSMO=1 the same source is `nlkalman-lsmo-seq`, scripts/nlkalman-lsmo-seq.sh in one process: the
+ * forward recursion with a smoother of lag 1 in place of the backward pass.
+ *
+ *   nlkalman-lsmo-seq [--flow tvl1|inv] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]
+ *     the script's arguments (no STP), SIG as above. As soon as frame i is filtered, frame i - 1 is smoothed against
+ *     flt2_i (seq_lag1_step, host/seq_step.h) and written as lsm1-%03d.tif; lsm1 of the last frame is its flt2. The
+ *     files are the script's: flt1- flt2- lsm1-%03d.tif, bflo-%03d.flo bocc-%03d.png and fflo-%03d.flo focc-%03d.png,
+ *     the last two under the number of the LATER frame. SPM = "no": no smoothing, no fflo / focc / lsm1.
+ *     --flow tvl1 (default) the script's second TV-L1 flow flt2_{i-1} -> flt2_i per frame; --flow inv: the backward
+ *     flow of frame i inverted (nlk_dev_flow_invert) in its place. Only the previous frame's outputs stay resident. */
 #include <errno.h>
 #include <math.h>
 #include <pthread.h>
@@ -76,7 +87,10 @@
 #ifndef NLK_SEQ_GT
 #define NLK_SEQ_GT 0
 #endif
-#define PROG (NLK_SEQ_GT ? "nlkalman-seq-gt" : "nlkalman-seq")
+#ifndef NLK_SEQ_LSMO
+#define NLK_SEQ_LSMO 0
+#endif
+#define PROG (NLK_SEQ_GT ? "nlkalman-seq-gt" : NLK_SEQ_LSMO ? "nlkalman-lsmo-seq" : "nlkalman-seq")
 
 nlk_ctx *nlkalman_hip_context(void); /* libnlkalman.so: the process-wide device context */
 
@@ -365,8 +379,17 @@ static int finish_gt(const char *out, const double *d_sums, const double *d_ssim
 }
 
 int main(int argc, const char **argv) {
-  const int gt = NLK_SEQ_GT;
-  int want_ssim = 0;
+  const int gt = NLK_SEQ_GT, lsmo = NLK_SEQ_LSMO;
+  int want_ssim = 0, lag1 = SEQ_LAG1_TVL1;
+  if (lsmo && argc > 1 && !strcmp(argv[1], "--flow")) { /* the positional arguments follow its value */
+    if (argc < 3 || !(lag1 = seq_lag1_mode(argv[2]))) {
+      fprintf(stderr, "%s: --flow %s: want tvl1 or inv\n", PROG, argc < 3 ? "" : argv[2]);
+      return 1;
+    }
+    argv[2] = argv[0];
+    argv += 2;
+    argc -= 2;
+  }
   if (gt && argc > 1 && !strcmp(argv[1], "--ssim")) { /* the positional arguments follow it */
     want_ssim = 1;
     argv[1] = argv[0];
@@ -377,6 +400,9 @@ int main(int argc, const char **argv) {
     if (gt)
       fprintf(stderr, "usage: %s [--ssim] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
                       "  one-process equivalent of scripts/nlkalman-seq-gt.sh (see the header of main_seq.c)\n", argv[0]);
+    else if (lsmo)
+      fprintf(stderr, "usage: %s [--flow tvl1|inv] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
+                      "  one-process equivalent of scripts/nlkalman-lsmo-seq.sh (see the header of main_seq.c)\n", argv[0]);
     else
       fprintf(stderr, "usage: %s SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]\n"
                       "  one-process equivalent of scripts/nlkalman-seq.sh (see the header of main_seq.c)\n", argv[0]);
@@ -398,9 +424,9 @@ int main(int argc, const char **argv) {
   const int vst_given = vst && argv[4][3];
   const int auto_sigma = vst || !strcmp(argv[4], "auto"); /* sigma is known once the first frame is on the device */
   float sigma = auto_sigma ? 0.f : atof(argv[4]);
-  /* the gt script has no STP: its FPM SPM OPM are $6 $7 $8 */
-  const int a0 = gt ? 6 : 7;
-  const int stp = !gt && argc > 6 && atoi(argv[6]) > 0 ? atoi(argv[6]) : 1;
+  /* the gt and lsmo scripts have no STP: their FPM SPM OPM are $6 $7 $8 */
+  const int a0 = gt || lsmo ? 6 : 7;
+  const int stp = a0 == 7 && argc > 6 && atoi(argv[6]) > 0 ? atoi(argv[6]) : 1;
   const char *fpm = argc > a0 ? argv[a0] : "", *spm = argc > a0 + 1 ? argv[a0 + 1] : "";
   const char *opm = argc > a0 + 2 && argv[a0 + 2][0] ? argv[a0 + 2]
                     : gt ? "1 0.40 0.75 1 0.40 0.75" : "1 0.25 0.75 1 0.25 0.75";
@@ -416,21 +442,8 @@ int main(int argc, const char **argv) {
   struct nlkalman_params f1, f2, s1;
   seq_unset_params(&f1); seq_unset_params(&f2); seq_unset_params(&s1);
   int verbose = 0;
-  const struct cli_option sopts[] = {
-      {CLI_INT, 0, "s1_p", &s1.patch_sz, "patch size"},
-      {CLI_INT, 0, "s1_st", &s1.search_sz_t, "search region radius"},
-      {CLI_INT, 0, "s1_nt", &s1.npatches_t, "number of similar patches kalman"},
-      {CLI_INT, 0, "s1_nt_agg", &s1.npatches_tagg, "number of similar patches kalman spatial average"},
-      {CLI_FLOAT, 0, "s1_bt", &s1.beta_t, "noise multiplier in kalman filtering"},
-      {CLI_FLOAT, 0, "s1_l", &s1.dista_lambda, "noisy patch weight in patch distance"},
-      {CLI_INT, 'v', "verbose", &verbose, "verbose output"},
-      {CLI_END, 0, NULL, NULL, NULL}};
   seq_parse_fpm("nlkalman-seq (FPM)", fpm, &f1, &f2, &verbose);
-  if (smoothing) {
-    const char **av;
-    const int ac = seq_split("nlkalman-seq (SPM)", spm, &av);
-    cli_parse(sopts, "nlkalman-seq (SPM)", "smoothing parameters", ac, av);
-  }
+  if (smoothing) seq_parse_spm("nlkalman-seq (SPM)", spm, &s1, &verbose);
   if (f1.patch_sz == 0 || f2.patch_sz == 0) {
     fprintf(stderr, "nlkalman-seq: both filtering iterations are needed (f1_p, f2_p != 0)\n");
     return 1;
@@ -459,6 +472,7 @@ int main(int argc, const char **argv) {
   size_t bytes = 0;
   float *d_rgb = NULL, *d_noisy = NULL, *d_tmp = NULL, *d_warp = NULL, *d_g0 = NULL, *d_g1 = NULL;
   float *d_flow = NULL, *d_occ = NULL, *flt1 = NULL;
+  float *d_fflow = NULL, *d_focc = NULL, *d_lsm1 = NULL; /* lsmo: the forward flow, its mask and the smoothed frame */
   float **flt2 = calloc(nframes, sizeof(float *));  /* kept for the backward pass */
   struct nlk_tvl1_params of;
   /* gt: the clean frames (all of them kept for the smoother's measures, else one buffer), the squared-error
@@ -501,6 +515,9 @@ int main(int argc, const char **argv) {
       d_rgb = dev_frame(bytes); d_noisy = dev_frame(bytes); d_tmp = dev_frame(bytes); d_warp = dev_frame(bytes);
       d_g0 = dev_frame((size_t)w * h * 4); d_g1 = dev_frame((size_t)w * h * 4); d_occ = dev_frame((size_t)w * h * 4);
       d_flow = dev_frame((size_t)w * h * 8);
+      if (lsmo && smoothing) {
+        d_fflow = dev_frame((size_t)w * h * 8); d_focc = dev_frame((size_t)w * h * 4); d_lsm1 = dev_frame(bytes);
+      }
       pool_init(bytes > (size_t)w * h * 8 ? bytes : (size_t)w * h * 8);
       if (Q.nthreads > 0) {
         void *hp = NULL;
@@ -591,16 +608,29 @@ int main(int argc, const char **argv) {
                                   t ? flt2[t - 1] : NULL, n1, n2};
     CHK(seq_forward_step(&step));
     if (t > 0) { /* the flow and its mask (script lines 57-73) */
-      write_dev(path_of(out, "bflo1-%03d.flo", i), d_flow, w, h, 2);
-      write_dev(path_of(out, "bocc1-%03d.png", i), d_occ, w, h, 1);
+      write_dev(path_of(out, lsmo ? "bflo-%03d.flo" : "bflo1-%03d.flo", i), d_flow, w, h, 2);
+      write_dev(path_of(out, lsmo ? "bocc-%03d.png" : "bocc1-%03d.png", i), d_occ, w, h, 1);
     }
     write_frame(path_of(out, OUTNAME("flt1"), i), n1, d_tmp, w, h, ch, SUM(0, t), SSIM(0, t), clean[t]);
     write_frame(path_of(out, OUTNAME("flt2"), i), n2, d_tmp, w, h, ch, SUM(1, t), SSIM(1, t), clean[t]);
+    if (lsmo && smoothing && t > 0) { /* smooth the previous frame (script lines 87-108) */
+      const struct seq_lag1 lag = {C, w, h, ch, sigma, &s1, lag1, fs2, dw2, th2, d_tmp, d_warp, d_g0, d_g1, d_flow,
+                                   d_fflow, d_focc, flt2[t - 1], n2, d_lsm1};
+      CHK(seq_lag1_step(&lag));
+      write_dev(path_of(out, "fflo-%03d.flo", i), d_fflow, w, h, 2);
+      write_dev(path_of(out, "focc-%03d.png", i), d_focc, w, h, 1);
+      write_frame(path_of(out, "lsm1-%03d.tif", i - 1), d_lsm1, d_tmp, w, h, ch, NULL, NULL, NULL);
+      if (verbose) printf("frame %d smoothed\n", i - 1);
+    }
     if (flt1) nlk_dev_free(C, flt1);
     flt1 = n1;
     flt2[t] = n2;
-    if (!smoothing && t > 0) { nlk_dev_free(C, flt2[t - 1]); flt2[t - 1] = NULL; }
+    if ((!smoothing || lsmo) && t > 0) { nlk_dev_free(C, flt2[t - 1]); flt2[t - 1] = NULL; }
     if (verbose) printf("frame %d filtered\n", i);
+  }
+  if (lsmo) { /* the last frame's lsm1 is its flt2 (script lines 112-116) */
+    if (smoothing) write_frame(path_of(out, "lsm1-%03d.tif", lfr), flt2[nframes - 1], d_tmp, w, h, ch, NULL, NULL, NULL);
+    return wq_finish();
   }
   if (!smoothing) return gt ? finish_gt(out, d_sums, d_ssims, 2, nframes, ch, (size_t)w * h * ch) : wq_finish(); /* script line 113 */
 

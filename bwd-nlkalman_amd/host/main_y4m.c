@@ -7,7 +7,13 @@
  *     --matrix 601|709|auto    auto (default): 709 when W >= 1280 or H > 576, else 601
  *     --range limited|full|auto   auto (default): the header's XCOLORRANGE, else limited
  *     --fpm "..."    nlkalman-flt options, as nlkalman-seq's FPM
- *     --opm "FSCALE DW TH"   flow parameters of the backward pass (default "1 0.25 0.75")
+ *     --opm "FSCALE DW TH [FSCALE2 DW2 TH2]"   flow parameters of the backward flow (default "1 0.25 0.75") and of
+ *                    the smoother's forward flow (default: the same three)
+ *     --smooth tvl1|inv   the lag-1 smoother (default: none): the output is the lsm1 frames of nlkalman-lsmo-seq
+ *                    (host/main_seq.c). Frame t - 1 is smoothed against flt2_t (seq_lag1_step, host/seq_step.h) and
+ *                    written when frame t has been filtered; the last frame goes out as its flt2. tvl1: a second TV-L1
+ *                    flow per frame, as the script; inv: the backward flow of frame t inverted (nlk_dev_flow_invert)
+ *     --spm "..."    nlkalman-smo options (--s1_p ...), as nlkalman-seq's SPM
  *     --frames N     stop after N frames
  *     --copy         convert to RGB and back only (no filter): the conversion path by itself
  *     --probe        no GPU, no output stream: parse IN, print one line
@@ -18,8 +24,9 @@
  * (host/seq_step.c) -> nlk_dev_opp2rgb on a copy of flt2 -> the inverse transform under SIG = vst ->
  * nlk_dev_rgb_to_yuv -> nlk_d2h -> the writer. The colour conversion runs on the GPU in both directions, so a 1080p
  * 4:2:0 8-bit frame crosses the link as 3.1 MB each way and the host encodes nothing. The output is the flt2 frames
- * in the input's format under the input's header line. Only flt1 and flt2 of the previous frame stay resident:
- * memory does not grow with the stream. There is no smoother (it runs backwards over a whole sequence).
+ * (with --smooth: the lsm1 frames, one frame later; as many frames go out as came in, in order) in the input's
+ * format under the input's header line. Only flt1 and flt2 of the previous frame stay resident: memory does not grow
+ * with the stream. The whole-sequence smoother runs backwards and has no place here; --smooth is its lag-1 form.
  *
  * A reader thread and a writer thread work beside the GPU on a ring of pinned payload buffers: frame t + 1 is read
  * while frame t is filtered and frame t - 1 is written. The two copies across the link (nlk_h2d, nlk_d2h: 3 MB each,
@@ -28,7 +35,7 @@
  *
  * Every diagnostic goes to stderr (stdout may be the stream), the "sigma ..." and "vst ..." lines of SIG = auto | vst
  * included. Exit status 0, or 1 on any error; a stream that ends inside a frame gives 1 after every complete frame
- * before it has been filtered and written. */
+ * before it has been filtered and written (with --smooth the last of them as its flt2). */
 #include <math.h>
 #include <pthread.h>
 #include <stdint.h>
@@ -132,6 +139,9 @@ static void *frame_get(long t) {
   slot_wait(i, INPUT, INPUT_END);
   return G.state[i] == INPUT ? G.buf[i] : NULL;
 }
+/* the buffer of frame t between frame_get and frame_put: once uploaded it is free to receive the output frame (with
+ * --smooth the main thread holds two slots, those of frames t - 1 and t; the reader and the writer share the rest) */
+static void *frame_buf(long t) { return G.buf[G.threads ? (int)(t % RING) : 0]; }
 /* the same buffer, now holding the output frame */
 static void frame_put(long t) {
   if (!G.threads) write_one(G.buf[0]);
@@ -152,17 +162,30 @@ static int probe(FILE *in, const struct y4m_header *hd, const char *range, int m
   return 0;
 }
 
+/* an opponent-space frame as output: RGB (transformed back under SIG = vst) -> codes -> buf */
+static int emit(void *buf, const float *d_opp, float *d_tmp, void *d_yuv, const struct y4m_header *hd, int ch,
+                const float *vst_ab, float vst_s) {
+  const size_t n = (size_t)hd->w * hd->h * ch;
+  CHK(nlk_d2d(C, d_tmp, d_opp, n * sizeof(float)));
+  CHK(nlk_dev_opp2rgb(C, d_tmp, hd->w, hd->h, ch));
+  if (vst_ab) CHK(nlk_dev_vst_inverse(C, d_tmp, d_tmp, n, ch, vst_ab, vst_s, 1));
+  CHK(nlk_dev_rgb_to_yuv(C, d_yuv, d_tmp, hd->w, hd->h, &hd->fmt));
+  CHK(nlk_d2h(C, buf, d_yuv, hd->frame_bytes));
+  return 0;
+}
+
 static int usage(void) {
   fprintf(stderr,
           "usage: %s [options] SIG [IN [OUT]]     IN, OUT: a file or \"-\" (default: stdin, stdout)\n"
           "  SIG: a number | auto | vst | vst:A,B\n"
-          "  --matrix 601|709|auto  --range limited|full|auto  --fpm \"...\"  --opm \"FSCALE DW TH\"\n"
-          "  --frames N  --copy  --probe  -v       (see the header of main_y4m.c)\n", PROG);
+          "  --matrix 601|709|auto  --range limited|full|auto  --fpm \"...\"  --opm \"FSCALE DW TH [FSCALE2 DW2 TH2]\"\n"
+          "  --smooth tvl1|inv  --spm \"...\"  --frames N  --copy  --probe  -v       (see the header of main_y4m.c)\n", PROG);
   return 1;
 }
 
 int main(int argc, const char **argv) {
   const char *matrix_s = "auto", *range_s = "auto", *fpm = "", *opm = "1 0.25 0.75", *pos[3] = {NULL, NULL, NULL};
+  const char *smooth_s = NULL, *spm = "";
   long max_frames = -1;
   int copy = 0, want_probe = 0, verbose = 0, npos = 0;
   for (int i = 1; i < argc; ++i) {
@@ -172,6 +195,8 @@ int main(int argc, const char **argv) {
     else if (!strcmp(a, "--range")) val = &range_s;
     else if (!strcmp(a, "--fpm")) val = &fpm;
     else if (!strcmp(a, "--opm")) val = &opm;
+    else if (!strcmp(a, "--smooth")) val = &smooth_s;
+    else if (!strcmp(a, "--spm")) val = &spm;
     if (val) {
       if (++i >= argc) { fprintf(stderr, "%s: %s needs a value\n", PROG, a); return 1; }
       *val = argv[i];
@@ -205,10 +230,17 @@ int main(int argc, const char **argv) {
   const int vst_given = vst && sig[3];
   const int auto_sigma = vst || !strcmp(sig, "auto");
   float sigma = auto_sigma ? 0.f : atof(sig);
-  int fs = 1;
-  float dw = 0.25f, th = 0.75f;
-  if (sscanf(opm, "%d %f %f", &fs, &dw, &th) != 3) {
-    fprintf(stderr, "%s: --opm must hold 3 numbers: FSCALE DW TH\n", PROG);
+  int fs = 1, fs2 = 1;
+  float dw = 0.25f, th = 0.75f, dw2 = 0.25f, th2 = 0.75f;
+  const int nopm = sscanf(opm, "%d %f %f %d %f %f", &fs, &dw, &th, &fs2, &dw2, &th2);
+  if (nopm != 3 && nopm != 6) {
+    fprintf(stderr, "%s: --opm must hold 3 or 6 numbers: FSCALE DW TH [FSCALE2 DW2 TH2]\n", PROG);
+    return 1;
+  }
+  if (nopm == 3) { fs2 = fs; dw2 = dw; th2 = th; }
+  int smooth = SEQ_LAG1_OFF;
+  if (smooth_s && !(smooth = seq_lag1_mode(smooth_s))) {
+    fprintf(stderr, "%s: --smooth %s: want tvl1 or inv\n", PROG, smooth_s);
     return 1;
   }
   int matrix = 0, range = -1;
@@ -221,6 +253,9 @@ int main(int argc, const char **argv) {
   struct nlkalman_params f1, f2;
   seq_unset_params(&f1); seq_unset_params(&f2);
   seq_parse_fpm(PROG " (--fpm)", fpm, &f1, &f2, &verbose);
+  struct nlkalman_params s1;
+  seq_unset_params(&s1);
+  if (smooth) seq_parse_spm(PROG " (--spm)", spm, &s1, &verbose);
   if (f1.patch_sz == 0 || f2.patch_sz == 0) {
     fprintf(stderr, "%s: both filtering iterations are needed (f1_p, f2_p != 0)\n", PROG);
     return 1;
@@ -286,7 +321,16 @@ int main(int argc, const char **argv) {
   if (!auto_sigma) {
     nlkalman_default_params(&f1, sigma, FLT1);
     nlkalman_default_params(&f2, sigma, FLT2);
+    nlkalman_default_params(&s1, sigma, SMO1);
   }
+  if (copy) smooth = SEQ_LAG1_OFF; /* (nothing is filtered) */
+  void *lp[3] = {0}; /* --smooth: the forward flow, its mask and the smoothed frame */
+  if (smooth) {
+    CHK(nlk_dev_alloc(C, &lp[0], npix * 8));
+    CHK(nlk_dev_alloc(C, &lp[1], npix * 4));
+    CHK(nlk_dev_alloc(C, &lp[2], bytes));
+  }
+  float *d_fflow = lp[0], *d_focc = lp[1], *d_lsm1 = lp[2];
 
   long t = 0;
   int failed = 0;
@@ -334,12 +378,29 @@ int main(int argc, const char **argv) {
       if (auto_sigma && t == 0) {
         nlkalman_default_params(&f1, sigma, FLT1);
         nlkalman_default_params(&f2, sigma, FLT2);
+        nlkalman_default_params(&s1, sigma, SMO1);
       }
       const int cur = (int)(t & 1), prv = cur ^ 1;
       const struct seq_step step = {C, w, h, ch, sigma, &f1, &f2, vst_ab, vst_s, fs, dw, th, d_rgb, d_noisy, d_tmp,
                                     d_warp, d_g0, d_g1, d_occ, d_flow, t ? flt1[prv] : NULL, t ? flt2[prv] : NULL,
                                     flt1[cur], flt2[cur]};
       CHK(seq_forward_step(&step));
+      if (smooth) { /* frame t - 1 goes out smoothed, into its own buffer; frame t waits for the next one */
+        if (t > 0) {
+          const struct seq_lag1 lag = {C, w, h, ch, sigma, &s1, smooth, fs2, dw2, th2, d_tmp, d_warp, d_g0, d_g1, d_flow,
+                                       d_fflow, d_focc, flt2[prv], flt2[cur], d_lsm1};
+          CHK(seq_lag1_step(&lag));
+          if (emit(frame_buf(t - 1), d_lsm1, d_tmp, d_yuv, &hd, ch, vst_ab, vst_s)) return 1;
+          frame_put(t - 1);
+          if (verbose) fprintf(stderr, "frame %ld smoothed\n", t);
+        }
+        if (verbose) fprintf(stderr, "frame %ld filtered\n", t + 1);
+        if (write_has_failed()) {
+          fprintf(stderr, "%s: %s\n", PROG, G.write_err);
+          return 1;
+        }
+        continue;
+      }
       CHK(nlk_d2d(C, d_tmp, flt2[cur], bytes));
       CHK(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
       if (vst_ab) CHK(nlk_dev_vst_inverse(C, d_tmp, d_tmp, npix * ch, ch, vst_ab, vst_s, 1));
@@ -354,6 +415,10 @@ int main(int argc, const char **argv) {
       return 1;
     }
   }
+  if (smooth && t > 0 && !failed) { /* the last frame goes out as its flt2 */
+    if (emit(frame_buf(t - 1), flt2[(t - 1) & 1], d_tmp, d_yuv, &hd, ch, vst_ab, vst_s)) return 1;
+    frame_put(t - 1);
+  }
   if (G.threads) {
     slot_set((int)(t % RING), OUTPUT_END); /* (slot t is the main thread's: it holds the end mark or a frame not used) */
     pthread_join(th_w, NULL);
@@ -363,5 +428,7 @@ int main(int argc, const char **argv) {
   if (G.write_failed) { fprintf(stderr, "%s: %s\n", PROG, G.write_err); failed = 1; }
   if (G.read_failed) { fprintf(stderr, "%s: frame %ld: %s\n", PROG, t + 1, G.read_err); failed = 1; }
   for (int i = 0; i < NDEV; ++i) nlk_dev_free(C, dp[i]);
+  for (int i = 0; i < 3; ++i)
+    if (lp[i]) nlk_dev_free(C, lp[i]);
   return failed;
 }

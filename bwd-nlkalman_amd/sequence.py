@@ -12,6 +12,11 @@ Forward (reference: scripts/nlkalman-seq.sh:30-115):
 Backward (reference: :117-150):
     smo_T = flt2_T;  smo_t = SMO1(flt2_t, warp(smo_{t+1}, TVL1(flt2_t -> smo_{t+1}), occ))
 
+Lag-1 smoother (reference: scripts/nlkalman-lsmo-seq.sh:87-116), SequenceFilter(lag1="tvl1" | "inv"):
+    after frame t:  lsm1_{t-1} = SMO1(flt2_{t-1}, warp(flt2_t, F_t, occ(F_t)))
+    F_t = TVL1(flt2_{t-1} -> flt2_t)  ("tvl1", the script's)  or  the inverse of flow_t  ("inv", Context.flow_invert)
+    lsm1 of the last frame is its flt2
+
 Frames are kept in the opponent colour space the filters work in (src/main-flt.c:335-343
 converts on read and back on write); the flow sees the luminance of the RGB frames like
 the tool does. Compared with the chain of processes this skips one opp->rgb->opp rounding
@@ -44,11 +49,21 @@ class SequenceFilter:
     pairs are measured on the first pushed frame (Context.estimate_noise_curve) or given for every channel; .noise
     holds them ([ch][2] float32), .sigma the scale S of the variance-stabilising transform (vst_scale). Every pushed
     frame is transformed first (Context.vst_forward), the recursion runs on transformed frames at sigma = S, and
-    download_rgb transforms back (Context.vst_inverse, mode 1)."""
+    download_rgb transforms back (Context.vst_inverse, mode 1).
+    lag1="tvl1" | "inv": after push() of frame t >= 1, .lsm1 is the smoothed frame t - 1 (device pointer, opponent
+    space, valid until the next push; None after the first push), .d_fflow / .d_focc the forward flow
+    flt2_{t-1} -> flt2_t and its mask: "tvl1" computes that flow (its iteration counts go to .lag1_flow_iterations),
+    "inv" inverts the backward flow of frame t (LAG1_INVERT_STEPS fixed-point steps). lag1_of_* / lag1_occ_th are the
+    second triple of OPM (default: the first). finish() gives the last frame's lsm1, its flt2."""
+
+    LAG1_INVERT_STEPS = 4   # SEQ_LAG1_INVERT_STEPS of host/seq_step.h
 
     def __init__(self, ctx, w, h, ch, sigma, f1=None, f2=None, s1=None, of_lambda=0.25, of_fscale=1,
-                 occ_th=0.75, keep_history=True):
+                 occ_th=0.75, keep_history=True, lag1=None, lag1_of_lambda=None, lag1_of_fscale=None,
+                 lag1_occ_th=None):
         pkg = _p()
+        if lag1 not in (None, "tvl1", "inv"):
+            raise ValueError(f"SequenceFilter(lag1={lag1!r}): want None, 'tvl1' or 'inv'")
         self.ctx, self.w, self.h, self.ch = ctx, w, h, ch
         self.f1, self.f2, self.s1 = f1, f2, s1
         self.sigma = None
@@ -72,6 +87,13 @@ class SequenceFilter:
         self._pool = []                      # released frame buffers (no hipMalloc / hipFree per frame)
         self.t = 0
         self.flow_iterations = []
+        self.lag1, self.lsm1 = lag1, None
+        if lag1:
+            self.of2 = pkg.tvl1_params(w, h, lam=of_lambda if lag1_of_lambda is None else lag1_of_lambda,
+                                       fscale=of_fscale if lag1_of_fscale is None else lag1_of_fscale)
+            self.occ_th2 = float(occ_th if lag1_occ_th is None else lag1_occ_th)
+            self.d_fflow, self.d_focc = a(w * h * 8), a(w * h * 4)
+            self.lag1_flow_iterations = []
         self.stage_s = None   # set to {} to have push() synchronise after each stage and add up its wall times (bench.py S1)
 
     def _resolve(self, sigma):
@@ -131,6 +153,8 @@ class SequenceFilter:
             c.warp_bicubic(self.d_warp, self.flt2, self.d_flow, self.d_occ, w, h, ch)
             c.filter_frame(n2, self.d_noisy, self.d_warp, n1, w, h, ch, sg, self.f2)
             mark("warp_flt2")
+        if self.lag1 and self.t > 0:
+            self._lag1_step(n2)
         if self.flt1:
             self._pool.append(self.flt1)
         if self.flt2 and self.history is None:
@@ -139,6 +163,30 @@ class SequenceFilter:
         if self.history is not None:
             self.history.append(n2)
         self.t += 1
+
+    def _lag1_step(self, d_cur):
+        """lsm1 of the previous frame from its flt2 (self.flt2), this frame's flt2 and, for "inv", this frame's
+        backward flow (self.d_flow): seq_lag1_step of host/seq_step.c"""
+        c, w, h, ch = self.ctx, self.w, self.h, self.ch
+        if self.lag1 == "inv":
+            c.flow_invert(self.d_fflow, self.d_flow, w, h, self.LAG1_INVERT_STEPS)
+        else:
+            for d_gray, d_opp in ((self.d_g0, self.flt2), (self.d_g1, d_cur)):
+                c.d2d(self.d_rgb, d_opp, self.nbytes)
+                c.opp2rgb(self.d_rgb, w, h, ch)
+                c.gray(d_gray, self.d_rgb, w, h, ch)
+            self.lag1_flow_iterations.append(c.tvl1_flow(self.d_fflow, self.d_g0, self.d_g1, w, h, self.of2))
+        c.occlusion_mask(self.d_focc, self.d_fflow, w, h, self.occ_th2)
+        c.warp_bicubic(self.d_warp, d_cur, self.d_fflow, self.d_focc, w, h, ch)
+        if self.lsm1 is None:
+            self.lsm1 = self._frame()
+        c.smooth_frame(self.lsm1, self.flt2, self.d_warp, None, w, h, ch, self.sigma, self.s1)
+
+    def finish(self):
+        """The last frame's lsm1: its flt2 (device pointer, opponent space)."""
+        if not self.lag1:
+            raise RuntimeError("SequenceFilter(lag1=None) has no lag-1 smoother to finish")
+        return self.flt2
 
     def _frame(self):
         return self._pool.pop() if self._pool else self.ctx.alloc(self.nbytes)

@@ -165,6 +165,20 @@ int nlk_dev_tvl1_flow(nlk_ctx *ctx, float *flow, const float *I0, const float *I
 int nlk_dev_gray(nlk_ctx *ctx, float *gray, const float *im, int w, int h, int ch);
 /* 255 where |backward-difference divergence of the flow| > th, else 0 */
 int nlk_dev_occlusion_mask(nlk_ctx *ctx, float *mask, const float *flow, int w, int h, float th);
+/* The inverse of a flow by fixed-point steps (the lag-1 smoother's forward flow from the filter's backward flow,
+ * DESIGN.md §9; restated in numpy by tests/flowinv_ref.py):
+ *   inv(q) = F_iters(q),  F_0(q) = -B(q),  F_{k+1}(q) = -B~(q + F_k(q))   (B = flow, w*h interleaved (u, v) pairs)
+ * B~ is the bilinear interpolation of B at (x + F.u, y + F.v), float32, every operation rounded by itself (no
+ * contraction), in this order:
+ *   X = fminf(fmaxf(x + F.u, 0), w - 1), Y likewise with h - 1;
+ *   x0 = (int)floorf(X) clamped to 0 .. w - 1, x1 = min(x0 + 1, w - 1), fx = X - x0, the same in y;
+ *   per component top = B00 + fx (B01 - B00), bot = B10 + fx (B11 - B10), val = top + fy (bot - top);  F = -val.
+ * iters = 0 gives -B. The indices are clamped after the conversion, so no input, non-finite ones included, makes the
+ * kernel read outside the array; what a non-finite B gives is unspecified at the pixels whose steps read it, and only
+ * there. The same input gives the same bits. One pass, no scratch, no atomics, h <= 262140 (more rows: NLK_EUNSUP);
+ * asynchronous on the context's stream. NLK_EINVAL for w or h < 1, iters outside 0..16, a NULL pointer or
+ * inv == flow (the arrays must not overlap); the context keeps working after a refused call. */
+int nlk_dev_flow_invert(nlk_ctx *ctx, float *inv, const float *flow, int w, int h, int iters);
 
 /* ---- multiscale wrapper (reference: lib/multiscale/multiscaler.cpp:21-107).
  * nlk_dev_image_dct: in-place whole-image DCT of an HWC image — forward = FFTW REDFT10 in both
