@@ -123,7 +123,7 @@ def frame(cur, prev, basic, sigma, P, smoother=False):
             if smoother and np0 == 0:
                 groups = [(px, py, _patch(cur, px, py, psz))]
                 vp = 0.0
-            wgt = f32(1.0) / f32(max(vp, 1e-6))
+            wgt = f32(1.0) / f32(vp if vp > 1e-6 else 1e-6)  # (the macro of src/nlkalman.c:15-18, :1824: a NaN vp gives 1e-6)
             if smoother:
                 mark = 1 if np0 else 0
             else:
