@@ -1,6 +1,7 @@
 /* cli_args.c — see cli_args.h. */
 #include "cli_args.h"
 #include "cli_server.h" /* cli_exit: leaves the process, or goes back to the resident server's loop */
+#include "nlkalman.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,6 +37,12 @@ static void take_value(const struct cli_option *o, int is_long, const char *inl,
     default:
       break;
   }
+}
+
+void cli_params_unset(struct nlkalman_params *p) {
+  p->patch_sz = p->search_sz_x = p->search_sz_t = -1;
+  p->npatches_x = p->npatches_t = p->npatches_tagg = -1;
+  p->dista_lambda = p->beta_x = p->beta_t = -1.f;
 }
 
 void cli_usage(const struct cli_option *opts, const char *prog, const char *description) {

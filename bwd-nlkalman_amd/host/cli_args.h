@@ -24,6 +24,31 @@ void cli_parse(const struct cli_option *opts, const char *prog, const char *desc
                int argc, const char **argv);
 void cli_usage(const struct cli_option *opts, const char *prog, const char *description);
 
+/* ---- the parameter options of nlkalman-flt and nlkalman-smo, stated once for every tool that takes them (the two
+ * tools, and the FPM / SPM strings of the sequence tools, host/seq_step.c). `p` points to a struct nlkalman_params. */
+struct nlkalman_params;
+/* every field "not given": nlkalman_default_params fills those in */
+void cli_params_unset(struct nlkalman_params *p);
+/* the nine rows of a filter stage: CLI_FILTER_ROWS("f1", &f1) gives --f1_p ... --f1_l */
+#define CLI_FILTER_ROWS(pfx, p)                                                                          \
+  {CLI_INT, 0, pfx "_p", &(p)->patch_sz, "patch size"},                                                  \
+  {CLI_INT, 0, pfx "_sx", &(p)->search_sz_x, "search radius (spatial filtering)"},                       \
+  {CLI_INT, 0, pfx "_st", &(p)->search_sz_t, "search radius (temporal filtering)"},                      \
+  {CLI_INT, 0, pfx "_nx", &(p)->npatches_x, "number of similar patches spatial"},                        \
+  {CLI_INT, 0, pfx "_nt", &(p)->npatches_t, "number of similar patches kalman"},                         \
+  {CLI_INT, 0, pfx "_nt_agg", &(p)->npatches_tagg, "number of similar patches kalman spatial average"},  \
+  {CLI_FLOAT, 0, pfx "_bx", &(p)->beta_x, "noise multiplier in spatial filtering"},                      \
+  {CLI_FLOAT, 0, pfx "_bt", &(p)->beta_t, "noise multiplier in kalman filtering"},                       \
+  {CLI_FLOAT, 0, pfx "_l", &(p)->dista_lambda, "noisy patch weight in patch distance"}
+/* the six rows of the smoother: CLI_SMOOTHER_ROWS("s1", &s1) gives --s1_p ... --s1_l */
+#define CLI_SMOOTHER_ROWS(pfx, p)                                                                        \
+  {CLI_INT, 0, pfx "_p", &(p)->patch_sz, "patch size"},                                                  \
+  {CLI_INT, 0, pfx "_st", &(p)->search_sz_t, "search region radius"},                                    \
+  {CLI_INT, 0, pfx "_nt", &(p)->npatches_t, "number of similar patches kalman"},                         \
+  {CLI_INT, 0, pfx "_nt_agg", &(p)->npatches_tagg, "number of similar patches kalman spatial average"},  \
+  {CLI_FLOAT, 0, pfx "_bt", &(p)->beta_t, "noise multiplier in kalman filtering"},                       \
+  {CLI_FLOAT, 0, pfx "_l", &(p)->dista_lambda, "noisy patch weight in patch distance"}
+
 /* One frame call per process is how the pipelines use the tools (scripts/nlkalman-seq.sh:39-41): the ~0.1 s the
  * HIP runtime takes to come up is on every call's critical path. cli_warm_start() begins creating the
  * process-wide device context on a second thread as soon as the arguments are known good, so that it overlaps

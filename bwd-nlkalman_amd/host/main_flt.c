@@ -21,12 +21,6 @@
 
 nlk_ctx *nlkalman_hip_context(void); /* process-wide context of libnlkalman.so */
 
-static void unset(struct nlkalman_params *p) {
-  p->patch_sz = p->search_sz_x = p->search_sz_t = -1;
-  p->npatches_x = p->npatches_t = p->npatches_tagg = -1;
-  p->dista_lambda = p->beta_x = p->beta_t = -1.f;
-}
-
 static void dump(const char *title, const struct nlkalman_params *p) {
   printf("%s\n\tpatch      %d\n\tsearch_x   %d\n\tsearch_t   %d\n\tnp_x       %d\n"
          "\tnp_t       %d\n\tnp_tagg    %d\n\tlambda     %g\n\tbeta_x     %g\n\tbeta_t     %g\n\n",
@@ -70,8 +64,8 @@ static int tool_body(int argc, const char **argv) {
   float sigma = 0.f;
   int verbose = 0;
   struct nlkalman_params f1, f2;
-  unset(&f1);
-  unset(&f2);
+  cli_params_unset(&f1);
+  cli_params_unset(&f2);
 
   const struct cli_option options[] = {
       {CLI_GROUP, 0, NULL, NULL, "Data i/o options"},
@@ -84,25 +78,9 @@ static int tool_body(int argc, const char **argv) {
       {CLI_STRING, 0, "flt21", &flt21_path, "output second filtering path"},
       {CLI_FLOAT, 's', "sigma", &sigma, "noise standard dev"},
       {CLI_GROUP, 0, NULL, NULL, "First filtering options"},
-      {CLI_INT, 0, "f1_p", &f1.patch_sz, "patch size"},
-      {CLI_INT, 0, "f1_sx", &f1.search_sz_x, "search radius (spatial filtering)"},
-      {CLI_INT, 0, "f1_st", &f1.search_sz_t, "search radius (temporal filtering)"},
-      {CLI_INT, 0, "f1_nx", &f1.npatches_x, "number of similar patches spatial"},
-      {CLI_INT, 0, "f1_nt", &f1.npatches_t, "number of similar patches kalman"},
-      {CLI_INT, 0, "f1_nt_agg", &f1.npatches_tagg, "number of similar patches kalman spatial average"},
-      {CLI_FLOAT, 0, "f1_bx", &f1.beta_x, "noise multiplier in spatial filtering"},
-      {CLI_FLOAT, 0, "f1_bt", &f1.beta_t, "noise multiplier in kalman filtering"},
-      {CLI_FLOAT, 0, "f1_l", &f1.dista_lambda, "noisy patch weight in patch distance"},
+      CLI_FILTER_ROWS("f1", &f1),
       {CLI_GROUP, 0, NULL, NULL, "Second filtering options"},
-      {CLI_INT, 0, "f2_p", &f2.patch_sz, "patch size"},
-      {CLI_INT, 0, "f2_sx", &f2.search_sz_x, "search radius (spatial filtering)"},
-      {CLI_INT, 0, "f2_st", &f2.search_sz_t, "search radius (temporal filtering)"},
-      {CLI_INT, 0, "f2_nx", &f2.npatches_x, "number of similar patches spatial"},
-      {CLI_INT, 0, "f2_nt", &f2.npatches_t, "number of similar patches kalman"},
-      {CLI_INT, 0, "f2_nt_agg", &f2.npatches_tagg, "number of similar patches kalman spatial average"},
-      {CLI_FLOAT, 0, "f2_bx", &f2.beta_x, "noise multiplier in spatial filtering"},
-      {CLI_FLOAT, 0, "f2_bt", &f2.beta_t, "noise multiplier in kalman filtering"},
-      {CLI_FLOAT, 0, "f2_l", &f2.dista_lambda, "noisy patch weight in patch distance"},
+      CLI_FILTER_ROWS("f2", &f2),
       {CLI_GROUP, 0, NULL, NULL, "Program options"},
       {CLI_INT, 'v', "verbose", &verbose, "verbose output"},
       {CLI_END, 0, NULL, NULL, NULL}};

@@ -8,6 +8,8 @@
  *     SIG   noise standard deviation, or "auto": measured on the first frame as the filter
  *           sees it (nlk_dev_estimate_sigma) and printed as "sigma %.9g" on stdout before
  *           that frame is filtered; the run is the one that number would have given  ($4)
+ *           (every form is read by seq_sig_parse and resolved on the first frame by seq_sig_resolve, host/seq_step.h:
+ *           nlkalman-y4m reads its SIG through the same two)
  *           "vst" or "vst:A,B": signal-dependent noise var = a y + b. With "vst" the pair of every channel is
  *           measured on the first frame as pushed (nlk_dev_estimate_noise_curve), with "vst:A,B" every channel
  *           uses the given pair. One line "vst a_0 b_0 ... sigma S" (S = nlk_vst_scale, each value "%.9g") goes to
@@ -27,7 +29,8 @@
  * What the script does with four processes and ~10 image files per frame (reference:
  * scripts/nlkalman-seq.sh:30-150) happens here through the device C-ABI: per frame
  * tvl1flow(noisy_t -> flt2_{t-1}) -> occlusion mask -> warp + FLT1 -> warp + FLT2, then
- * backwards tvl1flow(flt2_t -> smo1_{t+1}) -> mask -> warp + SMO1. Frames stay in the
+ * backwards tvl1flow(flt2_t -> smo1_{t+1}) -> mask -> warp + SMO1: seq_forward_step, then seq_lag1_step against
+ * smo1_{t+1} in its TV-L1 mode, on the work images of one struct seq_work (host/seq_step.h). Frames stay in the
  * opponent colour space between steps (the script's processes convert to RGB files and back:
  * a 1e-5 rounding on the 0..255 scale is the only numerical difference). Unlike the script,
  * flows and masks are always recomputed (it reuses files left by a previous run).
@@ -115,7 +118,7 @@ static struct {
   struct wjob *head, *tail;
   int pending, closed, failed, nthreads;
   pthread_t th[32];
-} Q = {PTHREAD_MUTEX_INITIALIZER, PTHREAD_COND_INITIALIZER, PTHREAD_COND_INITIALIZER, NULL, NULL, 0, 0, 0, 0, {0}};
+} Q = {.mu = PTHREAD_MUTEX_INITIALIZER, .more = PTHREAD_COND_INITIALIZER, .less = PTHREAD_COND_INITIALIZER};
 #define WQ_MAX_PENDING 12 /* arrays waiting or being written = pool size - 1 (25 MB each at 1080p RGB) */
 
 static void *wq_worker(void *arg) {
@@ -246,18 +249,14 @@ static char *path_of(const char *dir, const char *pattern, int i) {
   return full;
 }
 
-/* SIG = vst: the noise coefficients [ch][2] and the scale of the transform (vst_ab == NULL: no transform) */
-static float *vst_ab, vst_s;
+static struct seq_sig sig; /* SIG, resolved on the first frame */
 
-/* RGB copy of an opponent-space device frame -> file (takes ownership of `path`); d_sum != NULL: its squared
+/* RGB copy of an opponent-space device frame (seq_output_rgb) -> file (takes ownership of `path`); d_sum != NULL: its squared
  * error against d_clean goes to that device double first (the gt tool), d_ssim != NULL: its SSIM and those of its
  * channels to those 1 + ch device doubles (the gt tool with --ssim) */
 static void write_frame(char *path, const float *d_opp, float *d_tmp, int w, int h, int ch, double *d_sum,
                         double *d_ssim, const float *d_clean) {
-  const size_t bytes = (size_t)w * h * ch * sizeof(float);
-  CHK(nlk_d2d(C, d_tmp, d_opp, bytes));
-  CHK(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
-  if (vst_ab) CHK(nlk_dev_vst_inverse(C, d_tmp, d_tmp, (size_t)w * h * ch, ch, vst_ab, vst_s, 1));
+  CHK(seq_output_rgb(C, d_tmp, d_opp, w, h, ch, &sig));
   if (d_sum) CHK(nlk_dev_sqdiff_sum(C, d_sum, d_clean, d_tmp, (size_t)w * h * ch));
   if (d_ssim) CHK(nlk_dev_ssim(C, d_ssim, NULL, d_clean, d_tmp, w, h, ch, 255.f));
   write_dev(path, d_tmp, w, h, ch);
@@ -410,20 +409,16 @@ int main(int argc, const char **argv) {
   }
   const char *seq = argv[1], *out = argv[5];
   const int ffr = atoi(argv[2]), lfr = atoi(argv[3]);
-  const int vst = !strncmp(argv[4], "vst", 3); /* "vst" measures the curve, "vst:A,B" is told it */
-  float vst_a = 0.f, vst_b = 0.f;
+  const int sig_bad = seq_sig_parse(argv[4], &sig);
+  const int vst = sig.mode >= SEQ_SIG_VST, auto_sigma = sig.mode != SEQ_SIG_NUMBER;
   if (vst && gt) {
     fprintf(stderr, "%s: SIG = vst is not supported by the ground-truth loop\n", PROG);
     return 1;
   }
-  if (vst && argv[4][3] && (sscanf(argv[4] + 3, ":%f,%f", &vst_a, &vst_b) != 2 || !(vst_a >= 0.f) || !(vst_b >= 0.f) ||
-                            !(vst_a + vst_b > 0.f) || !(vst_a + vst_b <= 3e38f))) {
-    fprintf(stderr, "%s: SIG = %s: want vst or vst:A,B with A, B >= 0, not both 0\n", PROG, argv[4]);
+  if (sig_bad) {
+    fprintf(stderr, SEQ_SIG_WANT, PROG, argv[4]);
     return 1;
   }
-  const int vst_given = vst && argv[4][3];
-  const int auto_sigma = vst || !strcmp(argv[4], "auto"); /* sigma is known once the first frame is on the device */
-  float sigma = auto_sigma ? 0.f : atof(argv[4]);
   /* the gt and lsmo scripts have no STP: their FPM SPM OPM are $6 $7 $8 */
   const int a0 = gt || lsmo ? 6 : 7;
   const int stp = a0 == 7 && argc > 6 && atoi(argv[6]) > 0 ? atoi(argv[6]) : 1;
@@ -440,18 +435,13 @@ int main(int argc, const char **argv) {
 
   /* filter / smoother parameters: the options of nlkalman-flt and nlkalman-smo, same grammar */
   struct nlkalman_params f1, f2, s1;
-  seq_unset_params(&f1); seq_unset_params(&f2); seq_unset_params(&s1);
+  cli_params_unset(&f1); cli_params_unset(&f2); cli_params_unset(&s1);
   int verbose = 0;
   seq_parse_fpm("nlkalman-seq (FPM)", fpm, &f1, &f2, &verbose);
   if (smoothing) seq_parse_spm("nlkalman-seq (SPM)", spm, &s1, &verbose);
   if (f1.patch_sz == 0 || f2.patch_sz == 0) {
     fprintf(stderr, "nlkalman-seq: both filtering iterations are needed (f1_p, f2_p != 0)\n");
     return 1;
-  }
-  if (!auto_sigma) { /* (auto: once the first frame is on the device) */
-    nlkalman_default_params(&f1, sigma, FLT1);
-    nlkalman_default_params(&f2, sigma, FLT2);
-    nlkalman_default_params(&s1, sigma, SMO1);
   }
 
   /* every input frame must exist (script lines 19-28) */
@@ -470,11 +460,10 @@ int main(int argc, const char **argv) {
   wq_start();
   int w = 0, h = 0, ch = 0;
   size_t bytes = 0;
-  float *d_rgb = NULL, *d_noisy = NULL, *d_tmp = NULL, *d_warp = NULL, *d_g0 = NULL, *d_g1 = NULL;
-  float *d_flow = NULL, *d_occ = NULL, *flt1 = NULL;
-  float *d_fflow = NULL, *d_focc = NULL, *d_lsm1 = NULL; /* lsmo: the forward flow, its mask and the smoothed frame */
+  struct seq_work W = {0};
+  float *d_rgb = NULL, *flt1 = NULL;
+  float *d_lsm1 = NULL; /* lsmo: the smoothed frame (its flow and mask are W.d_fflow, W.d_focc) */
   float **flt2 = calloc(nframes, sizeof(float *));  /* kept for the backward pass */
-  struct nlk_tvl1_params of;
   /* gt: the clean frames (all of them kept for the smoother's measures, else one buffer), the squared-error
    * sums [pass][frame] (flt1, flt2, smo1) and the output names */
   float **clean = calloc(nframes, sizeof(float *));
@@ -512,12 +501,9 @@ int main(int argc, const char **argv) {
         CHK(nlk_dev_alloc(C, &d, sizeof(double) * 3 * nframes * (1 + ch)));
         d_ssims = (double *)d;
       }
-      d_rgb = dev_frame(bytes); d_noisy = dev_frame(bytes); d_tmp = dev_frame(bytes); d_warp = dev_frame(bytes);
-      d_g0 = dev_frame((size_t)w * h * 4); d_g1 = dev_frame((size_t)w * h * 4); d_occ = dev_frame((size_t)w * h * 4);
-      d_flow = dev_frame((size_t)w * h * 8);
-      if (lsmo && smoothing) {
-        d_fflow = dev_frame((size_t)w * h * 8); d_focc = dev_frame((size_t)w * h * 4); d_lsm1 = dev_frame(bytes);
-      }
+      d_rgb = dev_frame(bytes);
+      CHK(seq_work_alloc(C, &W, w, h, ch, lsmo && smoothing));
+      if (lsmo && smoothing) d_lsm1 = dev_frame(bytes);
       pool_init(bytes > (size_t)w * h * 8 ? bytes : (size_t)w * h * 8);
       if (Q.nthreads > 0) {
         void *hp = NULL;
@@ -553,7 +539,7 @@ int main(int argc, const char **argv) {
         fprintf(stderr, "%s: SIG = auto needs the noisy frame %s (there is no sigma to make it with)\n", PROG, npath);
         return 1;
       } else {
-        CHK(nlk_dev_awgn(C, d_rgb, clean[t], (size_t)w * h * ch, sigma, seed0 + (uint32_t)i));
+        CHK(nlk_dev_awgn(C, d_rgb, clean[t], (size_t)w * h * ch, sig.sigma, seed0 + (uint32_t)i));
         write_dev(npath, d_rgb, w, h, ch);
       }
     }
@@ -563,63 +549,32 @@ int main(int argc, const char **argv) {
       snprintf(next, sizeof next, seq, i + stp);
       ra_start(next);
     }
-    if (vst && t == 0) { /* the noise curve of the first frame, the scale of its transform = the sigma of the run */
-      if (ch > 16) { fprintf(stderr, "%s: SIG = vst: %d channels are too many\n", PROG, ch); return 1; }
-      vst_ab = malloc(sizeof(float) * 2 * ch);
-      if (vst_given) {
-        for (int c = 0; c < ch; ++c) { vst_ab[2 * c] = vst_a; vst_ab[2 * c + 1] = vst_b; }
-      } else {
-        float *d_curve = dev_frame(sizeof(float) * 2 * ch);
-        CHK(nlk_dev_estimate_noise_curve(C, d_curve, NULL, d_rgb, w, h, ch, NULL));
-        CHK(nlk_d2h(C, vst_ab, d_curve, sizeof(float) * 2 * ch));
-        nlk_dev_free(C, d_curve);
-      }
-      sigma = vst_s = nlk_vst_scale(vst_ab, ch);
-      if (!(sigma > 0.f)) {
-        fprintf(stderr, "%s: SIG = vst: the first frame gives no noise curve (a_0 = %g, b_0 = %g)\n", PROG,
-                (double)vst_ab[0], (double)vst_ab[1]);
-        return 1;
-      }
-      printf("vst");
-      for (int c = 0; c < 2 * ch; ++c) printf(" %.9g", (double)vst_ab[c]);
-      printf(" sigma %.9g\n", (double)sigma);
-      fflush(stdout);
-      nlkalman_default_params(&f1, sigma, FLT1);
-      nlkalman_default_params(&f2, sigma, FLT2);
-      nlkalman_default_params(&s1, sigma, SMO1);
-    } else if (auto_sigma && t == 0) { /* the noise level of the first frame, then every default that depends on it */
-      float *d_sigma = dev_frame(sizeof(float) * (1 + ch));
-      CHK(nlk_dev_estimate_sigma(C, d_sigma, NULL, d_rgb, w, h, ch, NULL));
-      CHK(nlk_d2h(C, &sigma, d_sigma, sizeof(float)));
-      nlk_dev_free(C, d_sigma);
-      if (!(sigma > 0.f)) {
-        fprintf(stderr, "%s: SIG = auto: the first frame gives sigma = %g\n", PROG, (double)sigma);
-        return 1;
-      }
-      printf("sigma %.9g\n", (double)sigma);
-      fflush(stdout);
-      nlkalman_default_params(&f1, sigma, FLT1);
-      nlkalman_default_params(&f2, sigma, FLT2);
-      nlkalman_default_params(&s1, sigma, SMO1);
+    if (t == 0) { /* sigma is known once the first frame is on the device, then every default that depends on it */
+      const int rc = seq_sig_resolve(C, &sig, d_rgb, w, h, ch, stdout, PROG);
+      if (rc == SEQ_SIG_REFUSED) return 1;
+      CHK(rc);
+      seq_default_params(&f1, &f2, &s1, sig.sigma);
     }
     float *n1 = dev_frame(bytes), *n2 = dev_frame(bytes);
-    const struct seq_step step = {C, w, h, ch, sigma, &f1, &f2, vst ? vst_ab : NULL, vst_s, fs1, dw1, th1, d_rgb,
-                                  d_noisy, d_tmp, d_warp, d_g0, d_g1, d_occ, d_flow, t ? flt1 : NULL,
-                                  t ? flt2[t - 1] : NULL, n1, n2};
+    const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .f1 = &f1, .f2 = &f2,
+                                  .fscale = fs1, .dw = dw1, .th = th1, .work = &W, .d_rgb = d_rgb,
+                                  .prev_flt1 = t ? flt1 : NULL, .prev_flt2 = t ? flt2[t - 1] : NULL,
+                                  .flt1 = n1, .flt2 = n2};
     CHK(seq_forward_step(&step));
     if (t > 0) { /* the flow and its mask (script lines 57-73) */
-      write_dev(path_of(out, lsmo ? "bflo-%03d.flo" : "bflo1-%03d.flo", i), d_flow, w, h, 2);
-      write_dev(path_of(out, lsmo ? "bocc-%03d.png" : "bocc1-%03d.png", i), d_occ, w, h, 1);
+      write_dev(path_of(out, lsmo ? "bflo-%03d.flo" : "bflo1-%03d.flo", i), W.d_flow, w, h, 2);
+      write_dev(path_of(out, lsmo ? "bocc-%03d.png" : "bocc1-%03d.png", i), W.d_occ, w, h, 1);
     }
-    write_frame(path_of(out, OUTNAME("flt1"), i), n1, d_tmp, w, h, ch, SUM(0, t), SSIM(0, t), clean[t]);
-    write_frame(path_of(out, OUTNAME("flt2"), i), n2, d_tmp, w, h, ch, SUM(1, t), SSIM(1, t), clean[t]);
+    write_frame(path_of(out, OUTNAME("flt1"), i), n1, W.d_tmp, w, h, ch, SUM(0, t), SSIM(0, t), clean[t]);
+    write_frame(path_of(out, OUTNAME("flt2"), i), n2, W.d_tmp, w, h, ch, SUM(1, t), SSIM(1, t), clean[t]);
     if (lsmo && smoothing && t > 0) { /* smooth the previous frame (script lines 87-108) */
-      const struct seq_lag1 lag = {C, w, h, ch, sigma, &s1, lag1, fs2, dw2, th2, d_tmp, d_warp, d_g0, d_g1, d_flow,
-                                   d_fflow, d_focc, flt2[t - 1], n2, d_lsm1};
+      const struct seq_lag1 lag = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = lag1,
+                                   .fscale = fs2, .dw = dw2, .th = th2, .work = &W, .d_fflow = W.d_fflow,
+                                   .d_focc = W.d_focc, .flt2 = flt2[t - 1], .next = n2, .smo1 = d_lsm1};
       CHK(seq_lag1_step(&lag));
-      write_dev(path_of(out, "fflo-%03d.flo", i), d_fflow, w, h, 2);
-      write_dev(path_of(out, "focc-%03d.png", i), d_focc, w, h, 1);
-      write_frame(path_of(out, "lsm1-%03d.tif", i - 1), d_lsm1, d_tmp, w, h, ch, NULL, NULL, NULL);
+      write_dev(path_of(out, "fflo-%03d.flo", i), W.d_fflow, w, h, 2);
+      write_dev(path_of(out, "focc-%03d.png", i), W.d_focc, w, h, 1);
+      write_frame(path_of(out, "lsm1-%03d.tif", i - 1), d_lsm1, W.d_tmp, w, h, ch, NULL, NULL, NULL);
       if (verbose) printf("frame %d smoothed\n", i - 1);
     }
     if (flt1) nlk_dev_free(C, flt1);
@@ -629,7 +584,7 @@ int main(int argc, const char **argv) {
     if (verbose) printf("frame %d filtered\n", i);
   }
   if (lsmo) { /* the last frame's lsm1 is its flt2 (script lines 112-116) */
-    if (smoothing) write_frame(path_of(out, "lsm1-%03d.tif", lfr), flt2[nframes - 1], d_tmp, w, h, ch, NULL, NULL, NULL);
+    if (smoothing) write_frame(path_of(out, "lsm1-%03d.tif", lfr), flt2[nframes - 1], W.d_tmp, w, h, ch, NULL, NULL, NULL);
     return wq_finish();
   }
   if (!smoothing) return gt ? finish_gt(out, d_sums, d_ssims, 2, nframes, ch, (size_t)w * h * ch) : wq_finish(); /* script line 113 */
@@ -637,28 +592,18 @@ int main(int argc, const char **argv) {
   /* ---- backward pass (script lines 117-150) */
   float **smo = calloc(nframes, sizeof(float *));
   smo[nframes - 1] = flt2[nframes - 1];
-  write_frame(path_of(out, OUTNAME("smo1"), ffr + (nframes - 1) * stp), smo[nframes - 1], d_tmp, w, h, ch,
+  write_frame(path_of(out, OUTNAME("smo1"), ffr + (nframes - 1) * stp), smo[nframes - 1], W.d_tmp, w, h, ch,
               SUM(2, nframes - 1), SSIM(2, nframes - 1), clean[nframes - 1]);
   for (t = nframes - 2; t >= 0; --t) {
     const int i = ffr + t * stp;
-    nlk_tvl1_default_params(&of);
-    of.lambda = dw2; of.fscale = fs2;
-    of.nscales = nlk_tvl1_scales(w, h, of.nscales, of.zfactor);
-    if (of.nscales < of.fscale) of.fscale = of.nscales;
-    CHK(nlk_d2d(C, d_rgb, flt2[t], bytes));
-    CHK(nlk_dev_opp2rgb(C, d_rgb, w, h, ch));
-    CHK(nlk_dev_gray(C, d_g0, d_rgb, w, h, ch));
-    CHK(nlk_d2d(C, d_tmp, smo[t + 1], bytes));
-    CHK(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
-    CHK(nlk_dev_gray(C, d_g1, d_tmp, w, h, ch));
-    CHK(nlk_dev_tvl1_flow(C, d_flow, d_g0, d_g1, w, h, &of, NULL));
-    CHK(nlk_dev_occlusion_mask(C, d_occ, d_flow, w, h, th2));
-    CHK(nlk_dev_warp_bicubic(C, d_warp, smo[t + 1], d_flow, d_occ, w, h, ch));
     smo[t] = dev_frame(bytes);
-    CHK(nlk_dev_smooth_frame(C, smo[t], flt2[t], d_warp, NULL, w, h, ch, sigma, &s1));
-    write_dev(path_of(out, "fflo-%03d.flo", i), d_flow, w, h, 2);
-    write_dev(path_of(out, "focc-%03d.png", i), d_occ, w, h, 1);
-    write_frame(path_of(out, OUTNAME("smo1"), i), smo[t], d_tmp, w, h, ch, SUM(2, t), SSIM(2, t), clean[t]);
+    const struct seq_lag1 back = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = SEQ_LAG1_TVL1,
+                                  .fscale = fs2, .dw = dw2, .th = th2, .work = &W, .d_fflow = W.d_flow,
+                                  .d_focc = W.d_occ, .flt2 = flt2[t], .next = smo[t + 1], .smo1 = smo[t]};
+    CHK(seq_lag1_step(&back));
+    write_dev(path_of(out, "fflo-%03d.flo", i), W.d_flow, w, h, 2);
+    write_dev(path_of(out, "focc-%03d.png", i), W.d_occ, w, h, 1);
+    write_frame(path_of(out, OUTNAME("smo1"), i), smo[t], W.d_tmp, w, h, ch, SUM(2, t), SSIM(2, t), clean[t]);
     if (verbose) printf("frame %d smoothed\n", i);
   }
   return gt ? finish_gt(out, d_sums, d_ssims, 3, nframes, ch, (size_t)w * h * ch) : wq_finish();

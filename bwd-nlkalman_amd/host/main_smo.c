@@ -55,9 +55,7 @@ static int tool_body(int argc, const char **argv) {
   float sigma = 0.f;
   int verbose = 0;
   struct nlkalman_params s1;
-  s1.patch_sz = s1.search_sz_x = s1.search_sz_t = -1;
-  s1.npatches_x = s1.npatches_t = s1.npatches_tagg = -1;
-  s1.dista_lambda = s1.beta_x = s1.beta_t = -1.f;
+  cli_params_unset(&s1);
 
   const struct cli_option options[] = {
       {CLI_GROUP, 0, NULL, NULL, "Data i/o options"},
@@ -68,12 +66,7 @@ static int tool_body(int argc, const char **argv) {
       {CLI_STRING, 0, "smo1", &smo1_path, "output smoothed frame"},
       {CLI_FLOAT, 's', "sigma", &sigma, "noise standard dev"},
       {CLI_GROUP, 0, NULL, NULL, "Smoothing options"},
-      {CLI_INT, 0, "s1_p", &s1.patch_sz, "patch size"},
-      {CLI_INT, 0, "s1_st", &s1.search_sz_t, "search region radius"},
-      {CLI_INT, 0, "s1_nt", &s1.npatches_t, "number of similar patches kalman"},
-      {CLI_INT, 0, "s1_nt_agg", &s1.npatches_tagg, "number of similar patches kalman spatial average"},
-      {CLI_FLOAT, 0, "s1_bt", &s1.beta_t, "noise multiplier in kalman filtering"},
-      {CLI_FLOAT, 0, "s1_l", &s1.dista_lambda, "noisy patch weight in patch distance"},
+      CLI_SMOOTHER_ROWS("s1", &s1),
       {CLI_GROUP, 0, NULL, NULL, "Program options"},
       {CLI_INT, 'v', "verbose", &verbose, "verbose output"},
       {CLI_END, 0, NULL, NULL, NULL}};

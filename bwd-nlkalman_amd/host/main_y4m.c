@@ -3,7 +3,8 @@
  *   ffmpeg -i in.mkv -f yuv4mpegpipe -strict -1 - | nlkalman-y4m 20 | ffmpeg -i - out.mkv
  *
  *   nlkalman-y4m [options] SIG [IN [OUT]]      IN, OUT: a file or "-" (default: stdin, stdout)
- *     SIG            a number | auto | vst | vst:A,B       (nlkalman-seq's forms and meaning, host/main_seq.c)
+ *     SIG            a number | auto | vst | vst:A,B       (nlkalman-seq's forms and meaning, host/main_seq.c, read
+ *                    and resolved by the same seq_sig_parse / seq_sig_resolve, host/seq_step.h)
  *     --matrix 601|709|auto    auto (default): 709 when W >= 1280 or H > 576, else 601
  *     --range limited|full|auto   auto (default): the header's XCOLORRANGE, else limited
  *     --fpm "..."    nlkalman-flt options, as nlkalman-seq's FPM
@@ -21,8 +22,8 @@
  *     -v             one line per frame on stderr
  *
  * Per frame: payload -> pinned buffer -> nlk_h2d -> nlk_dev_yuv_to_rgb -> the forward step of nlkalman-seq
- * (host/seq_step.c) -> nlk_dev_opp2rgb on a copy of flt2 -> the inverse transform under SIG = vst ->
- * nlk_dev_rgb_to_yuv -> nlk_d2h -> the writer. The colour conversion runs on the GPU in both directions, so a 1080p
+ * (host/seq_step.c) -> seq_output_rgb (nlk_dev_opp2rgb on a copy of flt2, the inverse transform under SIG = vst) ->
+ * nlk_dev_rgb_to_yuv -> nlk_d2h -> the writer (emit, for every frame that goes out). The colour conversion runs on the GPU in both directions, so a 1080p
  * 4:2:0 8-bit frame crosses the link as 3.1 MB each way and the host encodes nothing. The output is the flt2 frames
  * (with --smooth: the lsm1 frames, one frame later; as many frames go out as came in, in order) in the input's
  * format under the input's header line. Only flt1 and flt2 of the previous frame stay resident: memory does not grow
@@ -43,6 +44,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "cli_args.h"
 #include "nlk_hip.h"
 #include "nlkalman.h"
 #include "seq_step.h"
@@ -76,7 +78,7 @@ static struct {
   long max_frames;     /* < 0: no limit */
   int read_failed, write_failed;
   char read_err[Y4M_ERR_MAX], write_err[Y4M_ERR_MAX];
-} G = {PTHREAD_MUTEX_INITIALIZER, PTHREAD_COND_INITIALIZER, {0}, {0}, 0, NULL, NULL, NULL, -1, 0, 0, "", ""};
+} G = {.mu = PTHREAD_MUTEX_INITIALIZER, .cv = PTHREAD_COND_INITIALIZER, .max_frames = -1};
 
 static void slot_wait(int i, int s1, int s2) {
   pthread_mutex_lock(&G.mu);
@@ -162,14 +164,11 @@ static int probe(FILE *in, const struct y4m_header *hd, const char *range, int m
   return 0;
 }
 
-/* an opponent-space frame as output: RGB (transformed back under SIG = vst) -> codes -> buf */
-static int emit(void *buf, const float *d_opp, float *d_tmp, void *d_yuv, const struct y4m_header *hd, int ch,
-                const float *vst_ab, float vst_s) {
-  const size_t n = (size_t)hd->w * hd->h * ch;
-  CHK(nlk_d2d(C, d_tmp, d_opp, n * sizeof(float)));
-  CHK(nlk_dev_opp2rgb(C, d_tmp, hd->w, hd->h, ch));
-  if (vst_ab) CHK(nlk_dev_vst_inverse(C, d_tmp, d_tmp, n, ch, vst_ab, vst_s, 1));
-  CHK(nlk_dev_rgb_to_yuv(C, d_yuv, d_tmp, hd->w, hd->h, &hd->fmt));
+/* an RGB frame, or (sig != NULL) an opponent-space frame as output (seq_output_rgb), -> codes -> buf */
+static int emit(void *buf, const float *d_frame, float *d_tmp, void *d_yuv, const struct y4m_header *hd, int ch,
+                const struct seq_sig *sig) {
+  if (sig) CHK(seq_output_rgb(C, d_tmp, d_frame, hd->w, hd->h, ch, sig));
+  CHK(nlk_dev_rgb_to_yuv(C, d_yuv, sig ? d_tmp : d_frame, hd->w, hd->h, &hd->fmt));
   CHK(nlk_d2h(C, buf, d_yuv, hd->frame_bytes));
   return 0;
 }
@@ -217,19 +216,11 @@ int main(int argc, const char **argv) {
     else return usage();
   }
   if (npos < 1) return usage();
-  const char *sig = pos[0];
-
-  /* SIG, as nlkalman-seq reads it */
-  const int vst = !strncmp(sig, "vst", 3);
-  float vst_a = 0.f, vst_b = 0.f;
-  if (vst && sig[3] && (sscanf(sig + 3, ":%f,%f", &vst_a, &vst_b) != 2 || !(vst_a >= 0.f) || !(vst_b >= 0.f) ||
-                        !(vst_a + vst_b > 0.f) || !(vst_a + vst_b <= 3e38f))) {
-    fprintf(stderr, "%s: SIG = %s: want vst or vst:A,B with A, B >= 0, not both 0\n", PROG, sig);
+  struct seq_sig sig;
+  if (seq_sig_parse(pos[0], &sig)) {
+    fprintf(stderr, SEQ_SIG_WANT, PROG, pos[0]);
     return 1;
   }
-  const int vst_given = vst && sig[3];
-  const int auto_sigma = vst || !strcmp(sig, "auto");
-  float sigma = auto_sigma ? 0.f : atof(sig);
   int fs = 1, fs2 = 1;
   float dw = 0.25f, th = 0.75f, dw2 = 0.25f, th2 = 0.75f;
   const int nopm = sscanf(opm, "%d %f %f %d %f %f", &fs, &dw, &th, &fs2, &dw2, &th2);
@@ -251,10 +242,10 @@ int main(int argc, const char **argv) {
   else if (!strcmp(range_s, "full")) range = 1;
   else if (strcmp(range_s, "auto")) { fprintf(stderr, "%s: --range %s: want limited, full or auto\n", PROG, range_s); return 1; }
   struct nlkalman_params f1, f2;
-  seq_unset_params(&f1); seq_unset_params(&f2);
+  cli_params_unset(&f1); cli_params_unset(&f2);
   seq_parse_fpm(PROG " (--fpm)", fpm, &f1, &f2, &verbose);
   struct nlkalman_params s1;
-  seq_unset_params(&s1);
+  cli_params_unset(&s1);
   if (smooth) seq_parse_spm(PROG " (--spm)", spm, &s1, &verbose);
   if (f1.patch_sz == 0 || f2.patch_sz == 0) {
     fprintf(stderr, "%s: both filtering iterations are needed (f1_p, f2_p != 0)\n", PROG);
@@ -281,7 +272,7 @@ int main(int argc, const char **argv) {
     fprintf(stderr, "%s: a %d x %d frame is too large for the filter\n", PROG, w, h);
     return 1;
   }
-  const size_t bytes = (size_t)w * h * ch * sizeof(float), npix = (size_t)w * h;
+  const size_t bytes = (size_t)w * h * ch * sizeof(float);
   C = nlkalman_hip_context();
 
   /* the ring (pinned), or one pageable buffer */
@@ -308,29 +299,14 @@ int main(int argc, const char **argv) {
     return 1;
   }
 
-  enum { NDEV = 13 };
-  void *dp[NDEV] = {0};
-  const size_t want[NDEV] = {hd.frame_bytes, bytes, bytes, bytes, bytes, npix * 4, npix * 4, npix * 4, npix * 8,
-                             bytes, bytes, bytes, bytes};
-  for (int i = 0; i < NDEV; ++i) CHK(nlk_dev_alloc(C, &dp[i], want[i]));
-  void *d_yuv = dp[0];
-  float *d_rgb = dp[1], *d_noisy = dp[2], *d_tmp = dp[3], *d_warp = dp[4], *d_g0 = dp[5], *d_g1 = dp[6], *d_occ = dp[7],
-        *d_flow = dp[8];
-  float *flt1[2] = {dp[9], dp[10]}, *flt2[2] = {dp[11], dp[12]}; /* this frame's and the previous one's, by turns */
-  float *vst_ab = NULL, vst_s = 0.f;
-  if (!auto_sigma) {
-    nlkalman_default_params(&f1, sigma, FLT1);
-    nlkalman_default_params(&f2, sigma, FLT2);
-    nlkalman_default_params(&s1, sigma, SMO1);
-  }
   if (copy) smooth = SEQ_LAG1_OFF; /* (nothing is filtered) */
-  void *lp[3] = {0}; /* --smooth: the forward flow, its mask and the smoothed frame */
-  if (smooth) {
-    CHK(nlk_dev_alloc(C, &lp[0], npix * 8));
-    CHK(nlk_dev_alloc(C, &lp[1], npix * 4));
-    CHK(nlk_dev_alloc(C, &lp[2], bytes));
-  }
-  float *d_fflow = lp[0], *d_focc = lp[1], *d_lsm1 = lp[2];
+  struct seq_work W;
+  CHK(seq_work_alloc(C, &W, w, h, ch, smooth));
+  /* the codes; the RGB frame, flt1 and flt2 of this frame and the previous one, by turns, --smooth: the smoothed frame */
+  void *d_yuv = NULL, *fr[6] = {0};
+  CHK(nlk_dev_alloc(C, &d_yuv, hd.frame_bytes));
+  for (int i = 0; i < (smooth ? 6 : 5); ++i) CHK(nlk_dev_alloc(C, &fr[i], bytes));
+  float *d_rgb = fr[0], *flt1[2] = {fr[1], fr[2]}, *flt2[2] = {fr[3], fr[4]}, *d_lsm1 = fr[5];
 
   long t = 0;
   int failed = 0;
@@ -339,58 +315,26 @@ int main(int argc, const char **argv) {
     if (!buf) break;
     CHK(nlk_h2d(C, d_yuv, buf, hd.frame_bytes));
     CHK(nlk_dev_yuv_to_rgb(C, d_rgb, d_yuv, w, h, &hd.fmt));
-    const float *d_out = d_rgb;
     if (!copy) {
-      if (vst && t == 0) { /* the noise curve of the first frame, the scale of its transform = the sigma of the run */
-        vst_ab = malloc(sizeof(float) * 2 * ch);
-        if (vst_given) {
-          for (int c = 0; c < ch; ++c) { vst_ab[2 * c] = vst_a; vst_ab[2 * c + 1] = vst_b; }
-        } else {
-          void *d_curve = NULL;
-          CHK(nlk_dev_alloc(C, &d_curve, sizeof(float) * 2 * ch));
-          CHK(nlk_dev_estimate_noise_curve(C, d_curve, NULL, d_rgb, w, h, ch, NULL));
-          CHK(nlk_d2h(C, vst_ab, d_curve, sizeof(float) * 2 * ch));
-          nlk_dev_free(C, d_curve);
-        }
-        sigma = vst_s = nlk_vst_scale(vst_ab, ch);
-        if (!(sigma > 0.f)) {
-          fprintf(stderr, "%s: SIG = vst: the first frame gives no noise curve (a_0 = %g, b_0 = %g)\n", PROG,
-                  (double)vst_ab[0], (double)vst_ab[1]);
-          failed = 1;
-          break;
-        }
-        fprintf(stderr, "vst");
-        for (int c = 0; c < 2 * ch; ++c) fprintf(stderr, " %.9g", (double)vst_ab[c]);
-        fprintf(stderr, " sigma %.9g\n", (double)sigma);
-      } else if (auto_sigma && t == 0) { /* the noise level of the first frame */
-        void *d_sigma = NULL;
-        CHK(nlk_dev_alloc(C, &d_sigma, sizeof(float) * (1 + ch)));
-        CHK(nlk_dev_estimate_sigma(C, d_sigma, NULL, d_rgb, w, h, ch, NULL));
-        CHK(nlk_d2h(C, &sigma, d_sigma, sizeof(float)));
-        nlk_dev_free(C, d_sigma);
-        if (!(sigma > 0.f)) {
-          fprintf(stderr, "%s: SIG = auto: the first frame gives sigma = %g\n", PROG, (double)sigma);
-          failed = 1;
-          break;
-        }
-        fprintf(stderr, "sigma %.9g\n", (double)sigma);
-      }
-      if (auto_sigma && t == 0) {
-        nlkalman_default_params(&f1, sigma, FLT1);
-        nlkalman_default_params(&f2, sigma, FLT2);
-        nlkalman_default_params(&s1, sigma, SMO1);
+      if (t == 0) { /* sigma is known once the first frame is on the device, then every default that depends on it */
+        const int rc = seq_sig_resolve(C, &sig, d_rgb, w, h, ch, stderr, PROG);
+        if (rc == SEQ_SIG_REFUSED) { failed = 1; break; }
+        CHK(rc);
+        seq_default_params(&f1, &f2, &s1, sig.sigma);
       }
       const int cur = (int)(t & 1), prv = cur ^ 1;
-      const struct seq_step step = {C, w, h, ch, sigma, &f1, &f2, vst_ab, vst_s, fs, dw, th, d_rgb, d_noisy, d_tmp,
-                                    d_warp, d_g0, d_g1, d_occ, d_flow, t ? flt1[prv] : NULL, t ? flt2[prv] : NULL,
-                                    flt1[cur], flt2[cur]};
+      const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .f1 = &f1, .f2 = &f2,
+                                    .fscale = fs, .dw = dw, .th = th, .work = &W, .d_rgb = d_rgb,
+                                    .prev_flt1 = t ? flt1[prv] : NULL, .prev_flt2 = t ? flt2[prv] : NULL,
+                                    .flt1 = flt1[cur], .flt2 = flt2[cur]};
       CHK(seq_forward_step(&step));
       if (smooth) { /* frame t - 1 goes out smoothed, into its own buffer; frame t waits for the next one */
         if (t > 0) {
-          const struct seq_lag1 lag = {C, w, h, ch, sigma, &s1, smooth, fs2, dw2, th2, d_tmp, d_warp, d_g0, d_g1, d_flow,
-                                       d_fflow, d_focc, flt2[prv], flt2[cur], d_lsm1};
+          const struct seq_lag1 lag = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = smooth,
+                                       .fscale = fs2, .dw = dw2, .th = th2, .work = &W, .d_fflow = W.d_fflow,
+                                       .d_focc = W.d_focc, .flt2 = flt2[prv], .next = flt2[cur], .smo1 = d_lsm1};
           CHK(seq_lag1_step(&lag));
-          if (emit(frame_buf(t - 1), d_lsm1, d_tmp, d_yuv, &hd, ch, vst_ab, vst_s)) return 1;
+          if (emit(frame_buf(t - 1), d_lsm1, W.d_tmp, d_yuv, &hd, ch, &sig)) return 1;
           frame_put(t - 1);
           if (verbose) fprintf(stderr, "frame %ld smoothed\n", t);
         }
@@ -401,13 +345,9 @@ int main(int argc, const char **argv) {
         }
         continue;
       }
-      CHK(nlk_d2d(C, d_tmp, flt2[cur], bytes));
-      CHK(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
-      if (vst_ab) CHK(nlk_dev_vst_inverse(C, d_tmp, d_tmp, npix * ch, ch, vst_ab, vst_s, 1));
-      d_out = d_tmp;
     }
-    CHK(nlk_dev_rgb_to_yuv(C, d_yuv, d_out, w, h, &hd.fmt));
-    CHK(nlk_d2h(C, buf, d_yuv, hd.frame_bytes));
+    /* --copy: the RGB frame goes back as it is */
+    if (emit(buf, copy ? d_rgb : flt2[t & 1], W.d_tmp, d_yuv, &hd, ch, copy ? NULL : &sig)) return 1;
     frame_put(t);
     if (verbose) fprintf(stderr, "frame %ld %s\n", t + 1, copy ? "converted" : "filtered");
     if (write_has_failed()) { /* nobody reads the output any more: stop filtering (the process ends, threads and all) */
@@ -416,7 +356,7 @@ int main(int argc, const char **argv) {
     }
   }
   if (smooth && t > 0 && !failed) { /* the last frame goes out as its flt2 */
-    if (emit(frame_buf(t - 1), flt2[(t - 1) & 1], d_tmp, d_yuv, &hd, ch, vst_ab, vst_s)) return 1;
+    if (emit(frame_buf(t - 1), flt2[(t - 1) & 1], W.d_tmp, d_yuv, &hd, ch, &sig)) return 1;
     frame_put(t - 1);
   }
   if (G.threads) {
@@ -427,8 +367,9 @@ int main(int argc, const char **argv) {
   if (fflush(out) || (out != stdout && fclose(out))) { fprintf(stderr, "%s: write error\n", PROG); failed = 1; }
   if (G.write_failed) { fprintf(stderr, "%s: %s\n", PROG, G.write_err); failed = 1; }
   if (G.read_failed) { fprintf(stderr, "%s: frame %ld: %s\n", PROG, t + 1, G.read_err); failed = 1; }
-  for (int i = 0; i < NDEV; ++i) nlk_dev_free(C, dp[i]);
-  for (int i = 0; i < 3; ++i)
-    if (lp[i]) nlk_dev_free(C, lp[i]);
+  nlk_dev_free(C, d_yuv);
+  for (int i = 0; i < 6; ++i)
+    if (fr[i]) nlk_dev_free(C, fr[i]);
+  seq_work_free(C, &W);
   return failed;
 }

@@ -1,0 +1,19 @@
+/* seq_args.c — the grammar of the sequence tools' SIG argument (seq_step.h). Plain C: nothing of the device libraries
+ * is needed to link it. */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "seq_step.h"
+
+int seq_sig_parse(const char *text, struct seq_sig *sig) {
+  memset(sig, 0, sizeof *sig);
+  if (!strncmp(text, "vst", 3)) { /* "vst" measures the curve, "vst:A,B" is told it */
+    sig->mode = text[3] ? SEQ_SIG_VST_GIVEN : SEQ_SIG_VST;
+    return text[3] && (sscanf(text + 3, ":%f,%f", &sig->a, &sig->b) != 2 || !(sig->a >= 0.f) || !(sig->b >= 0.f) ||
+                       !(sig->a + sig->b > 0.f) || !(sig->a + sig->b <= 3e38f));
+  }
+  if (!strcmp(text, "auto")) sig->mode = SEQ_SIG_AUTO;
+  else sig->sigma = atof(text);
+  return 0;
+}

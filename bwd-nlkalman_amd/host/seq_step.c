@@ -6,12 +6,6 @@
 
 #include "cli_args.h"
 
-void seq_unset_params(struct nlkalman_params *p) {
-  p->patch_sz = p->search_sz_x = p->search_sz_t = -1;
-  p->npatches_x = p->npatches_t = p->npatches_tagg = -1;
-  p->dista_lambda = p->beta_x = p->beta_t = -1.f;
-}
-
 int seq_split(const char *prog, const char *s, const char ***argv_out) {
   char *buf = strdup(s ? s : "");
   int n = 1, cap = 64;
@@ -28,24 +22,8 @@ int seq_split(const char *prog, const char *s, const char ***argv_out) {
 void seq_parse_fpm(const char *prog, const char *fpm, struct nlkalman_params *f1, struct nlkalman_params *f2,
                    int *verbose) {
   const struct cli_option fopts[] = {
-      {CLI_INT, 0, "f1_p", &f1->patch_sz, "patch size"},
-      {CLI_INT, 0, "f1_sx", &f1->search_sz_x, "search radius (spatial filtering)"},
-      {CLI_INT, 0, "f1_st", &f1->search_sz_t, "search radius (temporal filtering)"},
-      {CLI_INT, 0, "f1_nx", &f1->npatches_x, "number of similar patches spatial"},
-      {CLI_INT, 0, "f1_nt", &f1->npatches_t, "number of similar patches kalman"},
-      {CLI_INT, 0, "f1_nt_agg", &f1->npatches_tagg, "number of similar patches kalman spatial average"},
-      {CLI_FLOAT, 0, "f1_bx", &f1->beta_x, "noise multiplier in spatial filtering"},
-      {CLI_FLOAT, 0, "f1_bt", &f1->beta_t, "noise multiplier in kalman filtering"},
-      {CLI_FLOAT, 0, "f1_l", &f1->dista_lambda, "noisy patch weight in patch distance"},
-      {CLI_INT, 0, "f2_p", &f2->patch_sz, "patch size"},
-      {CLI_INT, 0, "f2_sx", &f2->search_sz_x, "search radius (spatial filtering)"},
-      {CLI_INT, 0, "f2_st", &f2->search_sz_t, "search radius (temporal filtering)"},
-      {CLI_INT, 0, "f2_nx", &f2->npatches_x, "number of similar patches spatial"},
-      {CLI_INT, 0, "f2_nt", &f2->npatches_t, "number of similar patches kalman"},
-      {CLI_INT, 0, "f2_nt_agg", &f2->npatches_tagg, "number of similar patches kalman spatial average"},
-      {CLI_FLOAT, 0, "f2_bx", &f2->beta_x, "noise multiplier in spatial filtering"},
-      {CLI_FLOAT, 0, "f2_bt", &f2->beta_t, "noise multiplier in kalman filtering"},
-      {CLI_FLOAT, 0, "f2_l", &f2->dista_lambda, "noisy patch weight in patch distance"},
+      CLI_FILTER_ROWS("f1", f1),
+      CLI_FILTER_ROWS("f2", f2),
       {CLI_INT, 'v', "verbose", verbose, "verbose output"},
       {CLI_END, 0, NULL, NULL, NULL}};
   const char **av;
@@ -55,17 +33,18 @@ void seq_parse_fpm(const char *prog, const char *fpm, struct nlkalman_params *f1
 
 void seq_parse_spm(const char *prog, const char *spm, struct nlkalman_params *s1, int *verbose) {
   const struct cli_option sopts[] = {
-      {CLI_INT, 0, "s1_p", &s1->patch_sz, "patch size"},
-      {CLI_INT, 0, "s1_st", &s1->search_sz_t, "search region radius"},
-      {CLI_INT, 0, "s1_nt", &s1->npatches_t, "number of similar patches kalman"},
-      {CLI_INT, 0, "s1_nt_agg", &s1->npatches_tagg, "number of similar patches kalman spatial average"},
-      {CLI_FLOAT, 0, "s1_bt", &s1->beta_t, "noise multiplier in kalman filtering"},
-      {CLI_FLOAT, 0, "s1_l", &s1->dista_lambda, "noisy patch weight in patch distance"},
+      CLI_SMOOTHER_ROWS("s1", s1),
       {CLI_INT, 'v', "verbose", verbose, "verbose output"},
       {CLI_END, 0, NULL, NULL, NULL}};
   const char **av;
   const int ac = seq_split(prog, spm, &av);
   cli_parse(sopts, prog, "smoothing parameters", ac, av);
+}
+
+void seq_default_params(struct nlkalman_params *f1, struct nlkalman_params *f2, struct nlkalman_params *s1, float sigma) {
+  nlkalman_default_params(f1, sigma, FLT1);
+  nlkalman_default_params(f2, sigma, FLT2);
+  nlkalman_default_params(s1, sigma, SMO1);
 }
 
 int seq_lag1_mode(const char *name) {
@@ -80,60 +59,134 @@ int seq_lag1_mode(const char *name) {
     if (rc_ != NLK_OK) return rc_;    \
   } while (0)
 
+int seq_sig_resolve(nlk_ctx *C, struct seq_sig *sig, const float *d_rgb, int w, int h, int ch, FILE *report,
+                    const char *prog) {
+  if (sig->mode == SEQ_SIG_NUMBER) return NLK_OK;
+  const int vst = sig->mode != SEQ_SIG_AUTO;
+  if (vst && ch > SEQ_SIG_MAX_CH) {
+    fprintf(stderr, "%s: SIG = vst: %d channels are too many\n", prog, ch);
+    return SEQ_SIG_REFUSED;
+  }
+  if (sig->mode == SEQ_SIG_VST_GIVEN) {
+    for (int c = 0; c < ch; ++c) { sig->vst_ab[2 * c] = sig->a; sig->vst_ab[2 * c + 1] = sig->b; }
+  } else { /* the noise curve of the first frame, or its noise level (the first of 1 + ch values) */
+    const size_t bytes = sizeof(float) * (vst ? 2 * ch : 1 + ch);
+    void *d_est = NULL;
+    TRY(nlk_dev_alloc(C, &d_est, bytes));
+    int rc = vst ? nlk_dev_estimate_noise_curve(C, d_est, NULL, d_rgb, w, h, ch, NULL)
+                 : nlk_dev_estimate_sigma(C, d_est, NULL, d_rgb, w, h, ch, NULL);
+    if (rc == NLK_OK) rc = vst ? nlk_d2h(C, sig->vst_ab, d_est, bytes) : nlk_d2h(C, &sig->sigma, d_est, sizeof(float));
+    if (rc != NLK_OK) return rc;
+    nlk_dev_free(C, d_est);
+  }
+  if (vst) sig->sigma = sig->vst_s = nlk_vst_scale(sig->vst_ab, ch); /* the scale of the transform = the sigma of the run */
+  if (!(sig->sigma > 0.f)) {
+    if (vst)
+      fprintf(stderr, "%s: SIG = vst: the first frame gives no noise curve (a_0 = %g, b_0 = %g)\n", prog,
+              (double)sig->vst_ab[0], (double)sig->vst_ab[1]);
+    else
+      fprintf(stderr, "%s: SIG = auto: the first frame gives sigma = %g\n", prog, (double)sig->sigma);
+    return SEQ_SIG_REFUSED;
+  }
+  if (vst) {
+    fprintf(report, "vst");
+    for (int c = 0; c < 2 * ch; ++c) fprintf(report, " %.9g", (double)sig->vst_ab[c]);
+    fprintf(report, " ");
+  }
+  fprintf(report, "sigma %.9g\n", (double)sig->sigma);
+  fflush(report);
+  return NLK_OK;
+}
+
+int seq_work_alloc(nlk_ctx *C, struct seq_work *k, int w, int h, int ch, int with_smoother) {
+  const size_t npix = (size_t)w * h, bytes = npix * ch * sizeof(float);
+  const struct { float **p; size_t bytes; } want[] = {
+      {&k->d_noisy, bytes}, {&k->d_tmp, bytes}, {&k->d_warp, bytes}, {&k->d_g0, npix * 4}, {&k->d_g1, npix * 4},
+      {&k->d_occ, npix * 4}, {&k->d_flow, npix * 8}, {&k->d_fflow, npix * 8}, {&k->d_focc, npix * 4}};
+  memset(k, 0, sizeof *k);
+  for (int i = 0; i < (with_smoother ? 9 : 7); ++i) {
+    void *d = NULL;
+    TRY(nlk_dev_alloc(C, &d, want[i].bytes));
+    *want[i].p = (float *)d;
+  }
+  return NLK_OK;
+}
+
+void seq_work_free(nlk_ctx *C, struct seq_work *k) {
+  float *all[] = {k->d_noisy, k->d_tmp, k->d_warp, k->d_g0, k->d_g1, k->d_occ, k->d_flow, k->d_fflow, k->d_focc};
+  for (int i = 0; i < 9; ++i)
+    if (all[i]) nlk_dev_free(C, all[i]);
+  memset(k, 0, sizeof *k);
+}
+
+/* the TV-L1 parameters of a w x h flow with this finest scale and data weight (lambda) */
+static struct nlk_tvl1_params seq_flow_params(int w, int h, int fscale, float dw) {
+  struct nlk_tvl1_params of;
+  nlk_tvl1_default_params(&of);
+  of.lambda = dw; of.fscale = fscale;
+  of.nscales = nlk_tvl1_scales(w, h, of.nscales, of.zfactor);
+  if (of.nscales < of.fscale) of.fscale = of.nscales;
+  return of;
+}
+
+/* the gray image of an opponent-space frame, as the flow tool reads its RGB file (d_tmp: of the frame's size) */
+static int gray_of_opp(nlk_ctx *C, float *d_gray, float *d_tmp, const float *d_opp, int w, int h, int ch) {
+  TRY(nlk_d2d(C, d_tmp, d_opp, (size_t)w * h * ch * sizeof(float)));
+  TRY(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
+  return nlk_dev_gray(C, d_gray, d_tmp, w, h, ch);
+}
+
+int seq_output_rgb(nlk_ctx *C, float *d_tmp, const float *d_opp, int w, int h, int ch, const struct seq_sig *sig) {
+  const size_t n = (size_t)w * h * ch;
+  TRY(nlk_d2d(C, d_tmp, d_opp, n * sizeof(float)));
+  TRY(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
+  if (seq_sig_vst(sig)) TRY(nlk_dev_vst_inverse(C, d_tmp, d_tmp, n, ch, sig->vst_ab, sig->vst_s, 1));
+  return NLK_OK;
+}
+
 int seq_forward_step(const struct seq_step *s) {
   nlk_ctx *C = s->ctx;
+  const struct seq_work *k = s->work;
   const int w = s->w, h = s->h, ch = s->ch;
+  const float sigma = s->sig->sigma;
   const size_t bytes = (size_t)w * h * ch * sizeof(float);
-  if (s->vst_ab) TRY(nlk_dev_vst_forward(C, s->d_rgb, s->d_rgb, (size_t)w * h * ch, ch, s->vst_ab, s->vst_s));
-  TRY(nlk_d2d(C, s->d_noisy, s->d_rgb, bytes));
-  TRY(nlk_dev_rgb2opp(C, s->d_noisy, w, h, ch));
+  if (seq_sig_vst(s->sig))
+    TRY(nlk_dev_vst_forward(C, s->d_rgb, s->d_rgb, (size_t)w * h * ch, ch, s->sig->vst_ab, s->sig->vst_s));
+  TRY(nlk_d2d(C, k->d_noisy, s->d_rgb, bytes));
+  TRY(nlk_dev_rgb2opp(C, k->d_noisy, w, h, ch));
   if (!s->prev_flt2) {
-    TRY(nlk_dev_filter_frame(C, s->flt1, s->d_noisy, NULL, NULL, w, h, ch, s->sigma, s->f1));
-    TRY(nlk_dev_filter_frame(C, s->flt2, s->d_noisy, NULL, s->flt1, w, h, ch, s->sigma, s->f2));
+    TRY(nlk_dev_filter_frame(C, s->flt1, k->d_noisy, NULL, NULL, w, h, ch, sigma, s->f1));
+    TRY(nlk_dev_filter_frame(C, s->flt2, k->d_noisy, NULL, s->flt1, w, h, ch, sigma, s->f2));
     return NLK_OK;
   }
   /* backward flow noisy_t -> flt2_{t-1}, occlusion mask (script lines 57-73) */
-  struct nlk_tvl1_params of;
-  nlk_tvl1_default_params(&of);
-  of.lambda = s->dw; of.fscale = s->fscale;
-  of.nscales = nlk_tvl1_scales(w, h, of.nscales, of.zfactor);
-  if (of.nscales < of.fscale) of.fscale = of.nscales;
-  TRY(nlk_dev_gray(C, s->d_g0, s->d_rgb, w, h, ch));
-  TRY(nlk_d2d(C, s->d_tmp, s->prev_flt2, bytes));
-  TRY(nlk_dev_opp2rgb(C, s->d_tmp, w, h, ch));
-  TRY(nlk_dev_gray(C, s->d_g1, s->d_tmp, w, h, ch));
-  TRY(nlk_dev_tvl1_flow(C, s->d_flow, s->d_g0, s->d_g1, w, h, &of, NULL));
-  TRY(nlk_dev_occlusion_mask(C, s->d_occ, s->d_flow, w, h, s->th));
-  TRY(nlk_dev_warp_bicubic(C, s->d_warp, s->prev_flt1, s->d_flow, s->d_occ, w, h, ch));
-  TRY(nlk_dev_filter_frame(C, s->flt1, s->d_noisy, s->d_warp, NULL, w, h, ch, s->sigma, s->f1));
-  TRY(nlk_dev_warp_bicubic(C, s->d_warp, s->prev_flt2, s->d_flow, s->d_occ, w, h, ch));
-  TRY(nlk_dev_filter_frame(C, s->flt2, s->d_noisy, s->d_warp, s->flt1, w, h, ch, s->sigma, s->f2));
+  const struct nlk_tvl1_params of = seq_flow_params(w, h, s->fscale, s->dw);
+  TRY(nlk_dev_gray(C, k->d_g0, s->d_rgb, w, h, ch));
+  TRY(gray_of_opp(C, k->d_g1, k->d_tmp, s->prev_flt2, w, h, ch));
+  TRY(nlk_dev_tvl1_flow(C, k->d_flow, k->d_g0, k->d_g1, w, h, &of, NULL));
+  TRY(nlk_dev_occlusion_mask(C, k->d_occ, k->d_flow, w, h, s->th));
+  TRY(nlk_dev_warp_bicubic(C, k->d_warp, s->prev_flt1, k->d_flow, k->d_occ, w, h, ch));
+  TRY(nlk_dev_filter_frame(C, s->flt1, k->d_noisy, k->d_warp, NULL, w, h, ch, sigma, s->f1));
+  TRY(nlk_dev_warp_bicubic(C, k->d_warp, s->prev_flt2, k->d_flow, k->d_occ, w, h, ch));
+  TRY(nlk_dev_filter_frame(C, s->flt2, k->d_noisy, k->d_warp, s->flt1, w, h, ch, sigma, s->f2));
   return NLK_OK;
 }
 
 int seq_lag1_step(const struct seq_lag1 *s) {
   nlk_ctx *C = s->ctx;
+  const struct seq_work *k = s->work;
   const int w = s->w, h = s->h, ch = s->ch;
-  const size_t bytes = (size_t)w * h * ch * sizeof(float);
   if (s->mode == SEQ_LAG1_INV) {
-    TRY(nlk_dev_flow_invert(C, s->d_fflow, s->d_bflow, w, h, SEQ_LAG1_INVERT_STEPS));
+    TRY(nlk_dev_flow_invert(C, s->d_fflow, k->d_flow, w, h, SEQ_LAG1_INVERT_STEPS));
   } else {
-    /* forward flow flt2_{i-1} -> flt2_i, both as the flow tool reads their RGB files (script lines 90-96) */
-    struct nlk_tvl1_params of;
-    nlk_tvl1_default_params(&of);
-    of.lambda = s->dw; of.fscale = s->fscale;
-    of.nscales = nlk_tvl1_scales(w, h, of.nscales, of.zfactor);
-    if (of.nscales < of.fscale) of.fscale = of.nscales;
-    TRY(nlk_d2d(C, s->d_tmp, s->prev_flt2, bytes));
-    TRY(nlk_dev_opp2rgb(C, s->d_tmp, w, h, ch));
-    TRY(nlk_dev_gray(C, s->d_g0, s->d_tmp, w, h, ch));
-    TRY(nlk_d2d(C, s->d_tmp, s->cur_flt2, bytes));
-    TRY(nlk_dev_opp2rgb(C, s->d_tmp, w, h, ch));
-    TRY(nlk_dev_gray(C, s->d_g1, s->d_tmp, w, h, ch));
-    TRY(nlk_dev_tvl1_flow(C, s->d_fflow, s->d_g0, s->d_g1, w, h, &of, NULL));
+    /* forward flow flt2_i -> next, both as the flow tool reads their RGB files (script lines 90-96) */
+    const struct nlk_tvl1_params of = seq_flow_params(w, h, s->fscale, s->dw);
+    TRY(gray_of_opp(C, k->d_g0, k->d_tmp, s->flt2, w, h, ch));
+    TRY(gray_of_opp(C, k->d_g1, k->d_tmp, s->next, w, h, ch));
+    TRY(nlk_dev_tvl1_flow(C, s->d_fflow, k->d_g0, k->d_g1, w, h, &of, NULL));
   }
   TRY(nlk_dev_occlusion_mask(C, s->d_focc, s->d_fflow, w, h, s->th));
-  TRY(nlk_dev_warp_bicubic(C, s->d_warp, s->cur_flt2, s->d_fflow, s->d_focc, w, h, ch));
-  TRY(nlk_dev_smooth_frame(C, s->lsm1, s->prev_flt2, s->d_warp, NULL, w, h, ch, s->sigma, s->s1));
+  TRY(nlk_dev_warp_bicubic(C, k->d_warp, s->next, s->d_fflow, s->d_focc, w, h, ch));
+  TRY(nlk_dev_smooth_frame(C, s->smo1, s->flt2, k->d_warp, NULL, w, h, ch, s->sig->sigma, s->s1));
   return NLK_OK;
 }

@@ -1,14 +1,50 @@
-/* seq_step.h — what `nlkalman-seq`, `nlkalman-lsmo-seq` (host/main_seq.c) and `nlkalman-y4m` (host/main_y4m.c) share:
- * the FPM and SPM option strings, one step of the forward recursion and one step of the lag-1 smoother on
- * device-resident frames, through the device C-ABI. */
+/* seq_step.h — what `nlkalman-seq`, `nlkalman-seq-gt`, `nlkalman-lsmo-seq` (host/main_seq.c) and `nlkalman-y4m`
+ * (host/main_y4m.c) share, each stated once: the SIG argument (its grammar in host/seq_args.c, which links by itself;
+ * its first-frame resolution here), the FPM and SPM option strings, the work images, one step of the forward recursion,
+ * one smoother step (the lag-1 smoother's, and the whole-sequence backward pass's) and the way an opponent-space frame
+ * becomes an output frame, on device-resident frames through the device C-ABI. */
 #ifndef NLK_SEQ_STEP_H
 #define NLK_SEQ_STEP_H
+
+#include <stdio.h>
 
 #include "nlk_hip.h"
 #include "nlkalman.h"
 
-/* every field "not given": nlkalman_default_params fills those in */
-void seq_unset_params(struct nlkalman_params *p);
+/* ---- SIG: a number | auto | vst | vst:A,B */
+enum {
+  SEQ_SIG_NUMBER = 0, /* the noise standard deviation itself */
+  SEQ_SIG_AUTO,       /* measured on the first frame (nlk_dev_estimate_sigma) */
+  SEQ_SIG_VST,        /* var = a y + b, the pair of every channel measured on the first frame ... */
+  SEQ_SIG_VST_GIVEN   /* ... or given: every channel uses (a, b) */
+};
+#define SEQ_SIG_MAX_CH 16 /* channels of a variance-stabilised frame (nlk_dev_vst_forward's limit) */
+struct seq_sig {
+  int mode;
+  float a, b;                       /* SEQ_SIG_VST_GIVEN */
+  float sigma;                      /* the sigma of the run: SEQ_SIG_NUMBER as given, else 0 until seq_sig_resolve */
+  float vst_ab[2 * SEQ_SIG_MAX_CH]; /* vst, resolved: the coefficients [ch][2] and the scale of the transform */
+  float vst_s;
+};
+/* the grammar, nothing else: no device call, no output. 0, or 1 for a "vst..." that is neither "vst" nor "vst:A,B" with
+ * A, B >= 0, not both 0, A + B <= 3e38 (the caller prints SEQ_SIG_WANT under its own name); sig->mode is set either
+ * way. Anything that is not "auto" or "vst..." is a number as atof reads it. (host/seq_args.c) */
+int seq_sig_parse(const char *text, struct seq_sig *sig);
+#define SEQ_SIG_WANT "%s: SIG = %s: want vst or vst:A,B with A, B >= 0, not both 0\n" /* (prog, text) */
+/* the first frame's work, d_rgb being that frame as pushed: measures what the mode asks for, downloads it, fills
+ * sigma, vst_ab and vst_s and prints the one line "sigma S" | "vst a_0 b_0 ... sigma S" (each value "%.9g") to
+ * `report`; SEQ_SIG_NUMBER: nothing to do. Returns NLK_OK, the code of a failed device call (nlk_last_error has the
+ * message), or SEQ_SIG_REFUSED after a message under `prog` on stderr: more than SEQ_SIG_MAX_CH channels under vst,
+ * or a frame that gives no positive sigma. */
+#define SEQ_SIG_REFUSED 1
+int seq_sig_resolve(nlk_ctx *ctx, struct seq_sig *sig, const float *d_rgb, int w, int h, int ch, FILE *report,
+                    const char *prog);
+/* the coefficients of the transform, NULL when the run has none */
+static inline const float *seq_sig_vst(const struct seq_sig *sig) {
+  return sig->mode >= SEQ_SIG_VST ? sig->vst_ab : NULL;
+}
+
+/* ---- FPM, SPM (every field starts as cli_params_unset leaves it, host/cli_args.h) */
 /* "a b  c" -> argv {prog, a, b, c}; returns argc (the vector and its strings are never freed) */
 int seq_split(const char *prog, const char *s, const char ***argv_out);
 /* FPM: the options of nlkalman-flt (--f1_p ... --f2_l ..., -v) as one string, into f1, f2 and *verbose; exits with
@@ -17,34 +53,47 @@ void seq_parse_fpm(const char *prog, const char *fpm, struct nlkalman_params *f1
                    int *verbose);
 /* SPM: the options of nlkalman-smo (--s1_p ..., -v) as one string, into s1 and *verbose, likewise */
 void seq_parse_spm(const char *prog, const char *spm, struct nlkalman_params *s1, int *verbose);
+/* every field not given: the default of the three stages at this sigma */
+void seq_default_params(struct nlkalman_params *f1, struct nlkalman_params *f2, struct nlkalman_params *s1, float sigma);
 
+/* ---- the work images of a run */
+struct seq_work {
+  float *d_noisy, *d_tmp, *d_warp; /* of the frame's size ... */
+  float *d_g0, *d_g1, *d_occ;      /* ... of w * h floats ... */
+  float *d_flow;                   /* ... and of 2 * w * h: after a forward step d_flow and d_occ hold its flow and mask */
+  float *d_fflow, *d_focc;         /* with_smoother only: the lag-1 smoother's flow (2 * w * h) and mask (w * h) */
+};
+/* one device allocation per image; returns the first failing call's code (what was allocated stays for seq_work_free) */
+int seq_work_alloc(nlk_ctx *ctx, struct seq_work *k, int w, int h, int ch, int with_smoother);
+void seq_work_free(nlk_ctx *ctx, struct seq_work *k);
+
+/* ---- one step of the forward recursion */
 struct seq_step {
   nlk_ctx *ctx;
   int w, h, ch;
-  float sigma;
+  const struct seq_sig *sig; /* resolved */
   const struct nlkalman_params *f1, *f2;
-  const float *vst_ab; /* SIG = vst: the coefficients [ch][2] and the scale of the transform; NULL: no transform */
-  float vst_s;
-  int fscale;          /* backward flow: finest scale, data weight (lambda) and occlusion threshold */
+  int fscale;                /* backward flow: finest scale, data weight (lambda) and occlusion threshold */
   float dw, th;
-  float *d_rgb;        /* the noisy RGB frame; with vst_ab it is transformed in place */
-  float *d_noisy, *d_tmp, *d_warp; /* work images of the frame's size ... */
-  float *d_g0, *d_g1, *d_occ;      /* ... of w * h floats ... */
-  float *d_flow;                   /* ... and of 2 * w * h; afterwards d_flow and d_occ hold the flow and its mask */
+  const struct seq_work *work;
+  /* per frame: */
+  float *d_rgb;              /* the noisy RGB frame; under vst it is transformed in place */
   const float *prev_flt1, *prev_flt2; /* the previous frame's outputs (opponent space); both NULL on the first frame */
-  float *flt1, *flt2;  /* out: this frame's (opponent space) */
+  float *flt1, *flt2;        /* out: this frame's (opponent space) */
 };
 /* variance stabilisation, rgb2opp, then FLT1 and FLT2: spatial on the first frame, afterwards gray -> TV-L1 flow
  * noisy_t -> flt2_{t-1} -> occlusion mask -> warp + FLT1 -> warp + FLT2 (scripts/nlkalman-seq.sh:39-101).
  * Asynchronous on the context's stream; returns the first failing call's code (nlk_last_error has the message). */
 int seq_forward_step(const struct seq_step *s);
 
-/* ---- the lag-1 smoother (scripts/nlkalman-lsmo-seq.sh:87-108): as soon as frame i is filtered, frame i - 1 is
- * smoothed against flt2_i. The flow flt2_{i-1} -> flt2_i it needs comes from one of two sources. */
+/* ---- one smoother step: frame i is smoothed against a later frame's estimate. The lag-1 smoother
+ * (scripts/nlkalman-lsmo-seq.sh:87-108) does it as soon as frame i + 1 is filtered, next = flt2_{i+1}; the backward pass
+ * of the whole sequence (scripts/nlkalman-seq.sh:117-150) from the last frame down, next = smo1_{i+1}. The flow
+ * flt2_i -> next it needs comes from one of two sources. */
 enum {
   SEQ_LAG1_OFF = 0,
-  SEQ_LAG1_TVL1,  /* the script's: a second TV-L1 flow per frame */
-  SEQ_LAG1_INV    /* the inverse of the backward flow that the forward step of frame i left in d_flow */
+  SEQ_LAG1_TVL1,  /* the scripts': a TV-L1 flow of its own */
+  SEQ_LAG1_INV    /* the inverse of the backward flow that the forward step of frame i + 1 left in work->d_flow */
 };
 /* fixed-point steps of nlk_dev_flow_invert in SEQ_LAG1_INV: the count at which the inverted flow was measured against
  * the script's own flow on the CPU oracle (the table of DESIGN.md §9: within 0.05 dB at sigma <= 20, 0.15 dB at 40) */
@@ -55,21 +104,23 @@ int seq_lag1_mode(const char *name);
 struct seq_lag1 {
   nlk_ctx *ctx;
   int w, h, ch;
-  float sigma;
+  const struct seq_sig *sig; /* resolved */
   const struct nlkalman_params *s1;
-  int mode;            /* SEQ_LAG1_TVL1 | SEQ_LAG1_INV */
-  int fscale;          /* forward flow: finest scale and data weight (TVL1 only), occlusion threshold (both) */
+  int mode;                  /* SEQ_LAG1_TVL1 | SEQ_LAG1_INV */
+  int fscale;                /* forward flow: finest scale and data weight (TVL1 only), occlusion threshold (both) */
   float dw, th;
-  float *d_tmp, *d_warp;  /* work images of the frame's size ... */
-  float *d_g0, *d_g1;     /* ... and of w * h floats (TVL1 only) */
-  const float *d_bflow;   /* INV: the backward flow noisy_i -> flt2_{i-1} */
-  float *d_fflow, *d_focc; /* out: the forward flow (2 * w * h) and its mask (w * h) */
-  const float *prev_flt2, *cur_flt2; /* flt2_{i-1}, flt2_i (opponent space) */
-  float *lsm1;         /* out: the smoothed frame i - 1 (opponent space) */
+  const struct seq_work *work; /* d_tmp, d_warp; TVL1: d_g0, d_g1; INV: d_flow, the backward flow next -> flt2_i */
+  float *d_fflow, *d_focc;   /* out: the forward flow (2 * w * h) and its mask (w * h); TVL1 may use work->d_flow, d_occ */
+  /* per frame: */
+  const float *flt2, *next;  /* flt2_i and flt2_{i+1} | smo1_{i+1} (opponent space) */
+  float *smo1;               /* out: the smoothed frame i (opponent space) */
 };
-/* gray of both frames -> TV-L1 flow flt2_{i-1} -> flt2_i (or the inverted backward flow) -> occlusion mask -> warp of
- * flt2_i -> SMO1(flt1 = flt2_{i-1}, smo0 = the warp). Asynchronous on the context's stream; returns the first failing
- * call's code. */
+/* gray of both frames -> TV-L1 flow flt2_i -> next (or the inverted backward flow) -> occlusion mask -> warp of next ->
+ * SMO1(flt1 = flt2_i, smo0 = the warp). Asynchronous on the context's stream; returns the first failing call's code. */
 int seq_lag1_step(const struct seq_lag1 *s);
+
+/* ---- an opponent-space frame as output: d_tmp = its RGB copy, transformed back (nlk_dev_vst_inverse, mode 1) under
+ * vst. Returns the first failing call's code. */
+int seq_output_rgb(nlk_ctx *ctx, float *d_tmp, const float *d_opp, int w, int h, int ch, const struct seq_sig *sig);
 
 #endif
