@@ -40,6 +40,7 @@ HIP_SYMBOLS = [
     "nlk_sigma_default_params", "nlk_dev_estimate_sigma",
     "nlk_curve_default_params", "nlk_dev_estimate_noise_curve", "nlk_vst_scale", "nlk_dev_vst_forward",
     "nlk_dev_vst_inverse", "nlk_dev_noise_affine",
+    "nlk_nlf_build", "nlk_dev_nlf_forward", "nlk_dev_nlf_inverse",
     "nlk_yuv_format_from_tag", "nlk_yuv_frame_bytes", "nlk_dev_yuv_to_rgb", "nlk_dev_rgb_to_yuv",
     "nlk_dev_flow_invert",
 ]
@@ -84,6 +85,27 @@ class CurveParams(C.Structure):
 
 
 CURVE_BIN = np.dtype([("nblocks", np.int32), ("nsel", np.int32), ("mean", np.float32), ("var", np.float32)])
+
+
+NLF_MAX_CH, NLF_MAX_BINS, NLF_RHO = 16, 64, 0.25
+
+
+class NlfTable(C.Structure):
+    """struct nlk_nlf_table (include/nlk_hip.h): the noise-level-function transform nlk_nlf_build makes of a noise
+    curve's bins: knots x[0..nbins], per channel G[0..nbins], slope and islope[0..nbins-1], the noise level sigma at the
+    knots and the bins kept; s is the scale = the sigma of a run on transformed frames (NaN: a channel kept no bin)."""
+    _row = C.c_float * (NLF_MAX_BINS + 1)
+    _fields_ = [("ch", C.c_int), ("nbins", C.c_int), ("lo", C.c_float), ("hi", C.c_float), ("inv_dx", C.c_float),
+                ("s", C.c_float), ("kept", C.c_int * NLF_MAX_CH), ("x", _row), ("G", _row * NLF_MAX_CH),
+                ("slope", _row * NLF_MAX_CH), ("islope", _row * NLF_MAX_CH), ("sigma", _row * NLF_MAX_CH)]
+
+    def arrays(self):
+        """dict of numpy copies cut to the table's sizes: x [nbins+1], G and sigma [ch][nbins+1], slope and islope
+        [ch][nbins], kept [ch]"""
+        ch, nb = self.ch, self.nbins
+        a = {k: np.ctypeslib.as_array(getattr(self, k)).copy() for k in ("x", "G", "slope", "islope", "sigma", "kept")}
+        return dict(x=a["x"][:nb + 1], G=a["G"][:ch, :nb + 1], sigma=a["sigma"][:ch, :nb + 1],
+                    slope=a["slope"][:ch, :nb], islope=a["islope"][:ch, :nb], kept=a["kept"][:ch])
 
 
 class YuvFormat(C.Structure):
@@ -191,6 +213,9 @@ def hip():
         L.nlk_dev_vst_forward.argtypes = [vp, fp, fp, C.c_size_t, i, vp, f]
         L.nlk_dev_vst_inverse.argtypes = [vp, fp, fp, C.c_size_t, i, vp, f, i]
         L.nlk_dev_noise_affine.argtypes = [vp, fp, fp, C.c_size_t, i, vp, C.c_uint32]
+        L.nlk_nlf_build.argtypes = [C.POINTER(NlfTable), vp, i, i, f, f, f]
+        for fn in (L.nlk_dev_nlf_forward, L.nlk_dev_nlf_inverse):
+            fn.argtypes = [vp, fp, fp, C.c_size_t, i, C.POINTER(NlfTable)]
         L.nlk_yuv_format_from_tag.argtypes = [C.POINTER(YuvFormat), C.c_char_p]
         L.nlk_yuv_frame_bytes.argtypes = [i, i, C.POINTER(YuvFormat)]
         L.nlk_yuv_frame_bytes.restype = C.c_size_t
@@ -324,6 +349,20 @@ def vst_scale(ab, ch=None):
     if not s > 0:
         raise ValueError(f"vst_scale: refused coefficients {a.tolist()}")
     return s
+
+
+def nlf_build(bins, lo=0.0, hi=256.0, rho=NLF_RHO):
+    """nlk_nlf_build: the NlfTable of the bins [ch][nbins] (CURVE_BIN, as Context.estimate_noise_curve returns them)
+    measured over [lo, hi); host-only. Refused arguments raise ValueError; a channel that kept no bin gives a table
+    with s = NaN."""
+    b = np.ascontiguousarray(bins, CURVE_BIN)
+    if b.ndim != 2:
+        raise ValueError(f"nlf_build: want bins [ch][nbins], got shape {b.shape}")
+    t = NlfTable()
+    rc = hip().nlk_nlf_build(C.byref(t), b.ctypes.data, b.shape[0], b.shape[1], float(lo), float(hi), float(rho))
+    if rc:
+        raise ValueError(f"nlf_build: refused (rc={rc}): ch = {b.shape[0]}, nbins = {b.shape[1]}, lo = {lo}, hi = {hi}, rho = {rho}")
+    return t
 
 
 def default_params(sigma, mode, **over):
@@ -640,6 +679,22 @@ class Context:
         """The inverse transform: mode 0 algebraic (exact), mode 1 with the closed-form unbiasing terms."""
         a = _ab(ab, ch)
         self._chk(self.L.nlk_dev_vst_inverse(self.h, d_out, d_in, n, ch, a.ctypes.data, float(s), int(mode)))
+
+    # ---- a noise-level function of any shape (include/nlk_hip.h: nlk_nlf_build, nlk_dev_nlf_forward / _inverse)
+    def nlf_table(self, d_img, w, h, ch, rho=NLF_RHO, **params):
+        """The NlfTable of the device image d_img: the bins of estimate_noise_curve (params: the fields of
+        CurveParams) through nlf_build. Waits for the device."""
+        p = curve_params(**params)
+        return nlf_build(self.estimate_noise_curve(d_img, w, h, ch, **params)[1], p.lo, p.hi, rho)
+
+    def nlf_forward(self, d_out, d_in, n, ch, table):
+        """d_out[i] = the table's map of channel i mod ch at d_in[i]; the noise of the result has deviation table.s in
+        every channel. d_out may be d_in. Not synchronised (a table the context has not seen is uploaded first)."""
+        self._chk(self.L.nlk_dev_nlf_forward(self.h, d_out, d_in, n, ch, C.byref(table)))
+
+    def nlf_inverse(self, d_out, d_in, n, ch, table):
+        """The inverse map (algebraic: no unbiasing term)."""
+        self._chk(self.L.nlk_dev_nlf_inverse(self.h, d_out, d_in, n, ch, C.byref(table)))
 
     def noise_affine(self, d_out, d_in, n, ch, ab, seed):
         """d_out[i] = d_in[i] + sqrt(max(a_c d_in[i] + b_c, 0)) N_i with awgn's deviates N_i (d_out may be d_in)."""

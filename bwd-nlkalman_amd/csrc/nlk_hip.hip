@@ -188,12 +188,13 @@ void nlk_ctx_destroy(nlk_ctx* c) {
   hipStreamSynchronize(c->stream);
   if (c->aux_stream) hipStreamSynchronize(c->aux_stream);
   Buf* bufs[] = {&c->planes, &c->rowok, &c->vmap, &c->topk,
-                 &c->tinfo, &c->gcoords, &c->marks, &c->active, &c->acc, &c->tabs, &c->wide, &c->tv, &c->skew, &c->chase, &c->ms, &c->lz3, &c->sqd, &c->sig, &c->curve, &c->ssim,
+                 &c->tinfo, &c->gcoords, &c->marks, &c->active, &c->acc, &c->tabs, &c->wide, &c->tv, &c->skew, &c->chase, &c->ms, &c->lz3, &c->sqd, &c->sig, &c->curve, &c->ssim, &c->nlf,
                  &c->slab, &c->tflag, &c->hw_cur, &c->hw_prev, &c->hw_basic, &c->hw_out};
   for (Buf* b : bufs)
     if (b->p) hipFree(b->base ? b->base : b->p);
   for (int i = 0; i < c->lz3_nold; ++i) hipFree(c->lz3_old[i]);
   if (c->tv_host) (void)hipHostFree(c->tv_host);
+  free(c->nlf_host);
   if (c->ev) {
     for (int i = 0; i < nlk_ctx::MAXSETS * nlk_ctx::NEV; ++i) (void)hipEventDestroy(c->ev[i]);
     free(c->ev);

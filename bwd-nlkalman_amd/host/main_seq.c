@@ -18,6 +18,11 @@
  *           transformed frames at sigma = S with the defaults of S, and every flt1 / flt2 / smo1 frame is
  *           transformed back (nlk_dev_vst_inverse, mode 1) after opp2rgb, before it is downloaded. The gt tool
  *           refuses these forms.
+ *           "nlf": a noise-level function of any shape (gamma-encoded video, where var = a y + b does not hold). The
+ *           bins of the first frame's noise curve become a monotone piecewise-linear transform per channel
+ *           (nlk_nlf_build); one line "nlf kept K_0 ... sigma S" (K_c: the bins channel c kept, S the table's scale)
+ *           goes to stdout, and the run is vst's with nlk_dev_nlf_forward / nlk_dev_nlf_inverse in the transform's
+ *           places. The gt tool takes it as it takes "auto": every OUT/%03d.tif must exist.
  *     OUT   output folder: flt1-%03d.tif flt2-%03d.tif bflo1-%03d.flo bocc1-%03d.png and,
  *           unless SPM is "no", fflo-%03d.flo focc-%03d.png smo1-%03d.tif  ($5)
  *     FPM   extra nlkalman-flt options (--f1_p ... --f2_l ..., one string)  ($7)
@@ -410,7 +415,7 @@ int main(int argc, const char **argv) {
   const char *seq = argv[1], *out = argv[5];
   const int ffr = atoi(argv[2]), lfr = atoi(argv[3]);
   const int sig_bad = seq_sig_parse(argv[4], &sig);
-  const int vst = sig.mode >= SEQ_SIG_VST, auto_sigma = sig.mode != SEQ_SIG_NUMBER;
+  const int vst = seq_sig_vst(&sig) != NULL, auto_sigma = sig.mode != SEQ_SIG_NUMBER;
   if (vst && gt) {
     fprintf(stderr, "%s: SIG = vst is not supported by the ground-truth loop\n", PROG);
     return 1;
@@ -536,7 +541,7 @@ int main(int argc, const char **argv) {
         free(nz);
         free(npath);
       } else if (auto_sigma) {
-        fprintf(stderr, "%s: SIG = auto needs the noisy frame %s (there is no sigma to make it with)\n", PROG, npath);
+        fprintf(stderr, "%s: SIG = %s needs the noisy frame %s (there is no sigma to make it with)\n", PROG, argv[4], npath);
         return 1;
       } else {
         CHK(nlk_dev_awgn(C, d_rgb, clean[t], (size_t)w * h * ch, sig.sigma, seed0 + (uint32_t)i));

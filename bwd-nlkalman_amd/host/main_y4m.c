@@ -3,7 +3,7 @@
  *   ffmpeg -i in.mkv -f yuv4mpegpipe -strict -1 - | nlkalman-y4m 20 | ffmpeg -i - out.mkv
  *
  *   nlkalman-y4m [options] SIG [IN [OUT]]      IN, OUT: a file or "-" (default: stdin, stdout)
- *     SIG            a number | auto | vst | vst:A,B       (nlkalman-seq's forms and meaning, host/main_seq.c, read
+ *     SIG            a number | auto | vst | vst:A,B | nlf (nlkalman-seq's forms and meaning, host/main_seq.c, read
  *                    and resolved by the same seq_sig_parse / seq_sig_resolve, host/seq_step.h)
  *     --matrix 601|709|auto    auto (default): 709 when W >= 1280 or H > 576, else 601
  *     --range limited|full|auto   auto (default): the header's XCOLORRANGE, else limited
@@ -22,7 +22,7 @@
  *     -v             one line per frame on stderr
  *
  * Per frame: payload -> pinned buffer -> nlk_h2d -> nlk_dev_yuv_to_rgb -> the forward step of nlkalman-seq
- * (host/seq_step.c) -> seq_output_rgb (nlk_dev_opp2rgb on a copy of flt2, the inverse transform under SIG = vst) ->
+ * (host/seq_step.c) -> seq_output_rgb (nlk_dev_opp2rgb on a copy of flt2, the inverse transform under SIG = vst | nlf) ->
  * nlk_dev_rgb_to_yuv -> nlk_d2h -> the writer (emit, for every frame that goes out). The colour conversion runs on the GPU in both directions, so a 1080p
  * 4:2:0 8-bit frame crosses the link as 3.1 MB each way and the host encodes nothing. The output is the flt2 frames
  * (with --smooth: the lsm1 frames, one frame later; as many frames go out as came in, in order) in the input's
@@ -34,7 +34,7 @@
  * ~0.1 ms) are synchronous on the main thread, so the GPU waits for them: a known limit. NLK_SEQ_IO_THREADS=0, or a ring that cannot be allocated,
  * gives in-line I/O on one pageable buffer.
  *
- * Every diagnostic goes to stderr (stdout may be the stream), the "sigma ..." and "vst ..." lines of SIG = auto | vst
+ * Every diagnostic goes to stderr (stdout may be the stream), the "sigma ...", "vst ..." and "nlf ..." lines of SIG = auto | vst | nlf
  * included. Exit status 0, or 1 on any error; a stream that ends inside a frame gives 1 after every complete frame
  * before it has been filtered and written (with --smooth the last of them as its flt2). */
 #include <math.h>
@@ -176,7 +176,7 @@ static int emit(void *buf, const float *d_frame, float *d_tmp, void *d_yuv, cons
 static int usage(void) {
   fprintf(stderr,
           "usage: %s [options] SIG [IN [OUT]]     IN, OUT: a file or \"-\" (default: stdin, stdout)\n"
-          "  SIG: a number | auto | vst | vst:A,B\n"
+          "  SIG: a number | auto | vst | vst:A,B | nlf\n"
           "  --matrix 601|709|auto  --range limited|full|auto  --fpm \"...\"  --opm \"FSCALE DW TH [FSCALE2 DW2 TH2]\"\n"
           "  --smooth tvl1|inv  --spm \"...\"  --frames N  --copy  --probe  -v       (see the header of main_y4m.c)\n", PROG);
   return 1;

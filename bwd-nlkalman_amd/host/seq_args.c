@@ -14,6 +14,7 @@ int seq_sig_parse(const char *text, struct seq_sig *sig) {
                        !(sig->a + sig->b > 0.f) || !(sig->a + sig->b <= 3e38f));
   }
   if (!strcmp(text, "auto")) sig->mode = SEQ_SIG_AUTO;
+  else if (!strcmp(text, "nlf")) sig->mode = SEQ_SIG_NLF;
   else sig->sigma = atof(text);
   return 0;
 }

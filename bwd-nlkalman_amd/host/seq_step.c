@@ -59,9 +59,43 @@ int seq_lag1_mode(const char *name) {
     if (rc_ != NLK_OK) return rc_;    \
   } while (0)
 
+/* SIG = nlf: the bins of the first frame's noise curve (the estimator's defaults) as the table of nlk_nlf_build */
+static int seq_sig_resolve_nlf(nlk_ctx *C, struct seq_sig *sig, const float *d_rgb, int w, int h, int ch, FILE *report,
+                               const char *prog) {
+  if (ch > SEQ_SIG_MAX_CH) {
+    fprintf(stderr, "%s: SIG = nlf: %d channels are too many\n", prog, ch);
+    return SEQ_SIG_REFUSED;
+  }
+  struct nlk_curve_params p;
+  nlk_curve_default_params(&p);
+  struct nlk_curve_bin bins[SEQ_SIG_MAX_CH * NLK_NLF_MAX_BINS];
+  const size_t curve_bytes = sizeof(float) * 2 * ch, bin_bytes = sizeof(struct nlk_curve_bin) * ch * p.nbins;
+  void *d_est = NULL;
+  TRY(nlk_dev_alloc(C, &d_est, curve_bytes + bin_bytes));
+  struct nlk_curve_bin *d_bins = (struct nlk_curve_bin *)((char *)d_est + curve_bytes);
+  int rc = nlk_dev_estimate_noise_curve(C, d_est, d_bins, d_rgb, w, h, ch, &p);
+  if (rc == NLK_OK) rc = nlk_d2h(C, bins, d_bins, bin_bytes);
+  if (rc != NLK_OK) return rc;
+  nlk_dev_free(C, d_est);
+  if (nlk_nlf_build(&sig->nlf, bins, ch, p.nbins, p.lo, p.hi, NLK_NLF_RHO) != NLK_OK || !(sig->nlf.s > 0.f)) {
+    int c = 0;
+    while (c < ch - 1 && sig->nlf.kept[c] > 0) ++c;
+    fprintf(stderr, "%s: SIG = nlf: the first frame gives no noise level for channel %d (no bin of its curve is kept)\n",
+            prog, c);
+    return SEQ_SIG_REFUSED;
+  }
+  sig->sigma = sig->nlf.s; /* the scale of the transform = the sigma of the run */
+  fprintf(report, "nlf kept");
+  for (int c = 0; c < ch; ++c) fprintf(report, " %d", sig->nlf.kept[c]);
+  fprintf(report, " sigma %.9g\n", (double)sig->sigma);
+  fflush(report);
+  return NLK_OK;
+}
+
 int seq_sig_resolve(nlk_ctx *C, struct seq_sig *sig, const float *d_rgb, int w, int h, int ch, FILE *report,
                     const char *prog) {
   if (sig->mode == SEQ_SIG_NUMBER) return NLK_OK;
+  if (sig->mode == SEQ_SIG_NLF) return seq_sig_resolve_nlf(C, sig, d_rgb, w, h, ch, report, prog);
   const int vst = sig->mode != SEQ_SIG_AUTO;
   if (vst && ch > SEQ_SIG_MAX_CH) {
     fprintf(stderr, "%s: SIG = vst: %d channels are too many\n", prog, ch);
@@ -141,6 +175,7 @@ int seq_output_rgb(nlk_ctx *C, float *d_tmp, const float *d_opp, int w, int h, i
   TRY(nlk_d2d(C, d_tmp, d_opp, n * sizeof(float)));
   TRY(nlk_dev_opp2rgb(C, d_tmp, w, h, ch));
   if (seq_sig_vst(sig)) TRY(nlk_dev_vst_inverse(C, d_tmp, d_tmp, n, ch, sig->vst_ab, sig->vst_s, 1));
+  if (seq_sig_nlf(sig)) TRY(nlk_dev_nlf_inverse(C, d_tmp, d_tmp, n, ch, &sig->nlf));
   return NLK_OK;
 }
 
@@ -152,6 +187,7 @@ int seq_forward_step(const struct seq_step *s) {
   const size_t bytes = (size_t)w * h * ch * sizeof(float);
   if (seq_sig_vst(s->sig))
     TRY(nlk_dev_vst_forward(C, s->d_rgb, s->d_rgb, (size_t)w * h * ch, ch, s->sig->vst_ab, s->sig->vst_s));
+  if (seq_sig_nlf(s->sig)) TRY(nlk_dev_nlf_forward(C, s->d_rgb, s->d_rgb, (size_t)w * h * ch, ch, &s->sig->nlf));
   TRY(nlk_d2d(C, k->d_noisy, s->d_rgb, bytes));
   TRY(nlk_dev_rgb2opp(C, k->d_noisy, w, h, ch));
   if (!s->prev_flt2) {

@@ -11,12 +11,13 @@
 #include "nlk_hip.h"
 #include "nlkalman.h"
 
-/* ---- SIG: a number | auto | vst | vst:A,B */
+/* ---- SIG: a number | auto | vst | vst:A,B | nlf */
 enum {
   SEQ_SIG_NUMBER = 0, /* the noise standard deviation itself */
   SEQ_SIG_AUTO,       /* measured on the first frame (nlk_dev_estimate_sigma) */
   SEQ_SIG_VST,        /* var = a y + b, the pair of every channel measured on the first frame ... */
-  SEQ_SIG_VST_GIVEN   /* ... or given: every channel uses (a, b) */
+  SEQ_SIG_VST_GIVEN,  /* ... or given: every channel uses (a, b) */
+  SEQ_SIG_NLF         /* a noise-level function of any shape: the bins of the first frame's noise curve as a table */
 };
 #define SEQ_SIG_MAX_CH 16 /* channels of a variance-stabilised frame (nlk_dev_vst_forward's limit) */
 struct seq_sig {
@@ -25,23 +26,30 @@ struct seq_sig {
   float sigma;                      /* the sigma of the run: SEQ_SIG_NUMBER as given, else 0 until seq_sig_resolve */
   float vst_ab[2 * SEQ_SIG_MAX_CH]; /* vst, resolved: the coefficients [ch][2] and the scale of the transform */
   float vst_s;
+  struct nlk_nlf_table nlf;         /* nlf, resolved: the table of nlk_nlf_build (its s is the sigma of the run) */
 };
 /* the grammar, nothing else: no device call, no output. 0, or 1 for a "vst..." that is neither "vst" nor "vst:A,B" with
  * A, B >= 0, not both 0, A + B <= 3e38 (the caller prints SEQ_SIG_WANT under its own name); sig->mode is set either
- * way. Anything that is not "auto" or "vst..." is a number as atof reads it. (host/seq_args.c) */
+ * way. "nlf" is the whole word. Anything that is not "auto", "nlf" or "vst..." is a number as atof reads it.
+ * (host/seq_args.c) */
 int seq_sig_parse(const char *text, struct seq_sig *sig);
 #define SEQ_SIG_WANT "%s: SIG = %s: want vst or vst:A,B with A, B >= 0, not both 0\n" /* (prog, text) */
 /* the first frame's work, d_rgb being that frame as pushed: measures what the mode asks for, downloads it, fills
- * sigma, vst_ab and vst_s and prints the one line "sigma S" | "vst a_0 b_0 ... sigma S" (each value "%.9g") to
- * `report`; SEQ_SIG_NUMBER: nothing to do. Returns NLK_OK, the code of a failed device call (nlk_last_error has the
- * message), or SEQ_SIG_REFUSED after a message under `prog` on stderr: more than SEQ_SIG_MAX_CH channels under vst,
- * or a frame that gives no positive sigma. */
+ * sigma, vst_ab and vst_s (nlf: the table, from the bins of nlk_dev_estimate_noise_curve at its defaults and
+ * NLK_NLF_RHO) and prints the one line "sigma S" | "vst a_0 b_0 ... sigma S" | "nlf kept K_0 ... sigma S" (K_c: the
+ * bins channel c kept; each float "%.9g") to `report`; SEQ_SIG_NUMBER: nothing to do. Returns NLK_OK, the code of a failed device call (nlk_last_error has the
+ * message), or SEQ_SIG_REFUSED after a message under `prog` on stderr: more than SEQ_SIG_MAX_CH channels under vst
+ * or nlf, or a frame that gives no positive sigma (nlf: a channel that kept no bin). */
 #define SEQ_SIG_REFUSED 1
 int seq_sig_resolve(nlk_ctx *ctx, struct seq_sig *sig, const float *d_rgb, int w, int h, int ch, FILE *report,
                     const char *prog);
 /* the coefficients of the transform, NULL when the run has none */
 static inline const float *seq_sig_vst(const struct seq_sig *sig) {
-  return sig->mode >= SEQ_SIG_VST ? sig->vst_ab : NULL;
+  return sig->mode == SEQ_SIG_VST || sig->mode == SEQ_SIG_VST_GIVEN ? sig->vst_ab : NULL;
+}
+/* the table of the transform, NULL when the run has none */
+static inline const struct nlk_nlf_table *seq_sig_nlf(const struct seq_sig *sig) {
+  return sig->mode == SEQ_SIG_NLF ? &sig->nlf : NULL;
 }
 
 /* ---- FPM, SPM (every field starts as cli_params_unset leaves it, host/cli_args.h) */
@@ -77,7 +85,7 @@ struct seq_step {
   float dw, th;
   const struct seq_work *work;
   /* per frame: */
-  float *d_rgb;              /* the noisy RGB frame; under vst it is transformed in place */
+  float *d_rgb;              /* the noisy RGB frame; under vst and nlf it is transformed in place */
   const float *prev_flt1, *prev_flt2; /* the previous frame's outputs (opponent space); both NULL on the first frame */
   float *flt1, *flt2;        /* out: this frame's (opponent space) */
 };
@@ -119,8 +127,8 @@ struct seq_lag1 {
  * SMO1(flt1 = flt2_i, smo0 = the warp). Asynchronous on the context's stream; returns the first failing call's code. */
 int seq_lag1_step(const struct seq_lag1 *s);
 
-/* ---- an opponent-space frame as output: d_tmp = its RGB copy, transformed back (nlk_dev_vst_inverse, mode 1) under
- * vst. Returns the first failing call's code. */
+/* ---- an opponent-space frame as output: d_tmp = its RGB copy, transformed back under vst
+ * (nlk_dev_vst_inverse, mode 1) and nlf (nlk_dev_nlf_inverse). Returns the first failing call's code. */
 int seq_output_rgb(nlk_ctx *ctx, float *d_tmp, const float *d_opp, int w, int h, int ch, const struct seq_sig *sig);
 
 #endif

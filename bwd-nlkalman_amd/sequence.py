@@ -50,6 +50,9 @@ class SequenceFilter:
     holds them ([ch][2] float32), .sigma the scale S of the variance-stabilising transform (vst_scale). Every pushed
     frame is transformed first (Context.vst_forward), the recursion runs on transformed frames at sigma = S, and
     download_rgb transforms back (Context.vst_inverse, mode 1).
+    sigma="nlf": a noise-level function of any shape (gamma-encoded video), as `nlkalman-seq ... nlf`: .nlf is the
+    NlfTable of the first pushed frame (Context.nlf_table), .sigma its scale; Context.nlf_forward / nlf_inverse stand
+    where vst's transform stands.
     lag1="tvl1" | "inv": after push() of frame t >= 1, .lsm1 is the smoothed frame t - 1 (device pointer, opponent
     space, valid until the next push; None after the first push), .d_fflow / .d_focc the forward flow
     flt2_{t-1} -> flt2_t and its mask: "tvl1" computes that flow (its iteration counts go to .lag1_flow_iterations),
@@ -68,12 +71,14 @@ class SequenceFilter:
         self.f1, self.f2, self.s1 = f1, f2, s1
         self.sigma = None
         self.vst, self.noise, self.d_vst = False, None, None
+        self.nlf = None
+        self._nlf = isinstance(sigma, str) and sigma == "nlf"
         if isinstance(sigma, str) and sigma == "vst":
             self.vst = True
         elif isinstance(sigma, (tuple, list)) and len(sigma) == 3 and sigma[0] == "vst":
             self.vst = True
             self._resolve_vst(np.tile(np.asarray(sigma[1:], np.float32), (ch, 1)))
-        elif not (isinstance(sigma, str) and sigma == "auto"):
+        elif not (isinstance(sigma, str) and sigma in ("auto", "nlf")):
             self._resolve(float(sigma))
         self.of = pkg.tvl1_params(w, h, lam=of_lambda, fscale=of_fscale)
         self.occ_th = float(occ_th)
@@ -130,6 +135,17 @@ class SequenceFilter:
                 self.d_vst = c.alloc(self.nbytes)
             c.vst_forward(self.d_vst, d_noisy_rgb, w * h * ch, ch, self.noise, self.sigma)
             d_noisy_rgb = self.d_vst   # the flow sees the transformed frame too
+        if self._nlf:
+            if self.nlf is None:
+                table = c.nlf_table(d_noisy_rgb, w, h, ch)
+                if not table.s > 0:
+                    raise ValueError(f"SequenceFilter(sigma='nlf'): the first frame keeps {list(table.kept)[:ch]} bins")
+                self.nlf = table
+                self._resolve(float(table.s))
+            if self.d_vst is None:
+                self.d_vst = c.alloc(self.nbytes)
+            c.nlf_forward(self.d_vst, d_noisy_rgb, w * h * ch, ch, self.nlf)
+            d_noisy_rgb = self.d_vst
         if self.sigma is None:
             est = c.estimate_sigma(d_noisy_rgb, w, h, ch)[0]
             if not est > 0:
@@ -234,4 +250,6 @@ class SequenceFilter:
         c.opp2rgb(self.d_rgb, self.w, self.h, self.ch)
         if self.vst:
             c.vst_inverse(self.d_rgb, self.d_rgb, self.w * self.h * self.ch, self.ch, self.noise, self.sigma, 1)
+        if self.nlf is not None:
+            c.nlf_inverse(self.d_rgb, self.d_rgb, self.w * self.h * self.ch, self.ch, self.nlf)
         return c.download(self.d_rgb, (self.h, self.w, self.ch))

@@ -37,6 +37,8 @@
  *   nlk_dev_estimate_sigma              nothing: the reference is told sigma; this measures it
  *   nlk_dev_estimate_noise_curve, nlk_dev_vst_forward / _inverse, nlk_dev_noise_affine
  *                                       nothing: the reference knows white noise only
+ *   nlk_nlf_build, nlk_dev_nlf_forward / _inverse
+ *                                       nothing, likewise
  *   nlk_dev_ssim                        nothing: the reference measures the squared error only
  *   nlk_dev_yuv_to_rgb / nlk_dev_rgb_to_yuv, nlk_yuv_format_from_tag, nlk_yuv_frame_bytes
  *                                       nothing: the reference reads and writes RGB image files only
@@ -329,6 +331,58 @@ float nlk_vst_scale(const float *ab, int ch);
 int nlk_dev_vst_forward(nlk_ctx *ctx, float *out, const float *in, size_t n, int ch, const float *ab, float s);
 int nlk_dev_vst_inverse(nlk_ctx *ctx, float *out, const float *in, size_t n, int ch, const float *ab, float s,
                         int mode);
+
+/* ---- a noise-level function of any shape (gamma-encoded, tone-mapped video: DESIGN.md §9; restated in numpy by
+ * tests/nlf_ref.py). The bins of nlk_dev_estimate_noise_curve, without its line: a monotone piecewise-linear map per
+ * channel, with a knot at every bin edge, that makes the noise white.
+ *
+ * nlk_nlf_build (host only, double arithmetic, plain C: host/nlf_build.c links by itself) makes the table from the
+ * bins [ch][nbins] of one frame, downloaded, and the lo, hi, nbins they were measured with. Per channel:
+ *   a. K = the bins with n_q > 0 and v_q finite and > 0, in increasing q. A channel with an empty K makes the table
+ *      invalid: s = NaN (the other fields are then not to be used)
+ *   b. over neighbours in K (not in q): vs_k = (n_{k-1} v_{k-1} + 2 n_k v_k + n_{k+1} v_{k+1}) /
+ *      (n_{k-1} + 2 n_k + n_{k+1}), a missing neighbour left out of both sums
+ *   c. vs_k = max(vs_k, rho^2 median(vs)) (the mean of the two middle values for an even count): a clipped end, where
+ *      the measured variance collapses, gets a bounded gain
+ *   d. knots x_j = lo + j (hi - lo) / nbins, j = 0..nbins; v(x_j) = the linear interpolation of (m_k, vs_k), constant
+ *      outside [m_first, m_last]; sigma_j = sqrt(v(x_j))
+ *   e. at s = 1: kappa_j = 2 / (sigma_j + sigma_{j+1}), g(x_0) = 0, g(x_{j+1}) = g(x_j) + kappa_j (x_{j+1} - x_j); the
+ *      end segments extend linearly, so g is a bijection of the real line
+ *   f. span_c = g_c(255) - g_c(0), s = 255 / mean_c span_c: as with nlk_vst_scale the transformed frame keeps the
+ *      0..255 range, and s is the noise level of the run
+ *   g. x[j], G[c][j] = (float)(s (g_c(x_j) - g_c(0))) (black stays 0), slope[c][j] = (float)(s kappa_j),
+ *      islope[c][j] = (float)(1 / (s kappa_j)), inv_dx = (float)(nbins / (hi - lo)); sigma[c][j] = (float)sigma_j and
+ *      kept[c] = |K| for reports
+ * NLK_EINVAL for a NULL argument, ch outside 1..16, nbins outside 1..64, hi <= lo (or either not finite), rho outside
+ * (0, 1]; NLK_OK otherwise, also for an invalid table. NLK_NLF_RHO is the rho of the tools.
+ *
+ * nlk_dev_nlf_forward / nlk_dev_nlf_inverse apply it to n samples, the channel of sample i being i mod ch = the
+ * table's ch. float arithmetic, every operation rounded by itself:
+ *   forward   t = fminf(fmaxf((y - lo) inv_dx, 0), nbins - 1), j = (int)floorf(t), g = G[j] + (y - x[j]) slope[j]
+ *   inverse   j = the number of k in 1..nbins-1 with G[k] <= g, y = x[j] + (g - G[j]) islope[j]
+ * NaN gives NaN, +-inf passes through. The inverse is the algebraic one; it has no unbiasing term (a locally linear
+ * map needs none to first order). One pass; out may be in; asynchronous on the context's stream. The context keeps
+ * the device copy of the last table it was given: a table is uploaded when it differs from that one (which waits for
+ * the stream once), not on every call. NLK_EINVAL for a NULL argument, a table whose s is not positive and finite, and
+ * ch != the table's. */
+#define NLK_NLF_MAX_CH 16
+#define NLK_NLF_MAX_BINS 64
+#define NLK_NLF_RHO 0.25f
+struct nlk_nlf_table {
+  int ch, nbins;
+  float lo, hi, inv_dx;
+  float s;                                  /* the scale = the sigma of the run; NaN: a channel kept no bin */
+  int kept[NLK_NLF_MAX_CH];                 /* |K| per channel */
+  float x[NLK_NLF_MAX_BINS + 1];            /* knots, [0..nbins] */
+  float G[NLK_NLF_MAX_CH][NLK_NLF_MAX_BINS + 1];      /* [0..nbins] */
+  float slope[NLK_NLF_MAX_CH][NLK_NLF_MAX_BINS + 1];  /* [0..nbins-1] (the rest 0) */
+  float islope[NLK_NLF_MAX_CH][NLK_NLF_MAX_BINS + 1]; /* [0..nbins-1] */
+  float sigma[NLK_NLF_MAX_CH][NLK_NLF_MAX_BINS + 1];  /* sigma_j of the frame's own scale, [0..nbins] */
+};
+int nlk_nlf_build(struct nlk_nlf_table *t, const struct nlk_curve_bin *bins, int ch, int nbins, float lo, float hi,
+                  float rho);
+int nlk_dev_nlf_forward(nlk_ctx *ctx, float *out, const float *in, size_t n, int ch, const struct nlk_nlf_table *t);
+int nlk_dev_nlf_inverse(nlk_ctx *ctx, float *out, const float *in, size_t n, int ch, const struct nlk_nlf_table *t);
 
 /* nlk_dev_awgn with a deviation that follows the signal: out[i] = (float)((double)in[i] + sqrt(max(a_c in[i] + b_c,
  * 0)) g_i), c = i mod ch, g_i exactly the normal deviate nlk_dev_awgn draws for that index and seed; ab as above
