@@ -42,7 +42,7 @@ HIP_SYMBOLS = [
     "nlk_dev_vst_inverse", "nlk_dev_noise_affine",
     "nlk_nlf_build", "nlk_dev_nlf_forward", "nlk_dev_nlf_inverse",
     "nlk_yuv_format_from_tag", "nlk_yuv_frame_bytes", "nlk_dev_yuv_to_rgb", "nlk_dev_rgb_to_yuv",
-    "nlk_dev_flow_invert",
+    "nlk_dev_flow_invert", "nlk_bmflow_default_params", "nlk_dev_bm_flow",
 ]
 API_SYMBOLS = [
     "rgb2opp", "opp2rgb", "warp_bicubic", "nlkalman_default_params",
@@ -56,6 +56,12 @@ class Tvl1Params(C.Structure):
     _fields_ = [("tau", C.c_float), ("lam", C.c_float), ("theta", C.c_float),
                 ("nscales", C.c_int), ("fscale", C.c_int), ("zfactor", C.c_float),
                 ("nwarps", C.c_int), ("epsilon", C.c_float)]
+
+
+class BmflowParams(C.Structure):
+    """struct nlk_bmflow_params (include/nlk_hip.h): the finest level that is matched, the search radius (1..3) and the
+    smallest side of a pyramid level."""
+    _fields_ = [("fscale", C.c_int), ("radius", C.c_int), ("min_side", C.c_int)]
 
 
 class Params(C.Structure):
@@ -194,6 +200,9 @@ def hip():
         L.nlk_dev_gray.argtypes = [vp, fp, fp, i, i, i]
         L.nlk_dev_occlusion_mask.argtypes = [vp, fp, fp, i, i, f]
         L.nlk_dev_flow_invert.argtypes = [vp, fp, fp, i, i, i]
+        L.nlk_bmflow_default_params.argtypes = [C.POINTER(BmflowParams)]
+        L.nlk_bmflow_default_params.restype = None
+        L.nlk_dev_bm_flow.argtypes = [vp, fp, fp, fp, i, i, C.POINTER(BmflowParams)]
         L.nlk_dev_image_dct.argtypes = [vp, fp, i, i, i, i]
         L.nlk_dev_copy_block.argtypes = [vp, fp, i, fp, i, i, i, i]
         L.nlk_dev_lz3_down.argtypes = [vp, fp, fp, i, i, i]
@@ -295,6 +304,16 @@ def tvl1_params(w, h, **over):
         setattr(p, k, v)
     p.nscales = hip().nlk_tvl1_scales(w, h, p.nscales, p.zfactor)
     p.fscale = min(p.fscale, p.nscales)
+    return p
+
+
+def bmflow_params(fscale=None, radius=None, min_side=None):
+    """nlk_bmflow_default_params, with the fields given overridden."""
+    p = BmflowParams()
+    hip().nlk_bmflow_default_params(C.byref(p))
+    for k, v in (("fscale", fscale), ("radius", radius), ("min_side", min_side)):
+        if v is not None:
+            setattr(p, k, int(v))
     return p
 
 
@@ -545,6 +564,12 @@ class Context:
     def flow_invert(self, d_inv, d_flow, w, h, iters=4):
         """The inverse of a flow by `iters` fixed-point steps (nlk_dev_flow_invert; tests/flowinv_ref.py restates it)."""
         self._chk(self.L.nlk_dev_flow_invert(self.h, d_inv, d_flow, w, h, int(iters)))
+
+    def bm_flow(self, d_flow, d_i0, d_i1, w, h, fscale=None, radius=None, min_side=None):
+        """Block-matching flow I0 -> I1 into d_flow (w*h interleaved pairs, nlk_dev_bm_flow; tests/bmflow_ref.py restates
+        it). Parameters left None are nlk_bmflow_default_params' (1, 2, 16)."""
+        p = bmflow_params(fscale, radius, min_side)
+        self._chk(self.L.nlk_dev_bm_flow(self.h, d_flow, d_i0, d_i1, w, h, C.byref(p)))
 
     def image_dct(self, d_img, w, h, ch, inverse=False):
         self._chk(self.L.nlk_dev_image_dct(self.h, d_img, w, h, ch, int(inverse)))

@@ -93,6 +93,7 @@ struct nlk_ctx {
   void* lz3_old[16] = {};         // ... its outgrown allocations, freed with the context (a free would synchronise the
   int lz3_nold = 0;               //     device between the levels of a recompose)
   NlkBuf tv;                      // TV-L1 pyramids and work images
+  NlkBuf bm;                      // nlk_dev_bm_flow: pyramids, block vectors and the flows between levels (tu_bmflow.hip)
   NlkBuf sqd;                     // nlk_dev_sqdiff_sum: the per-workgroup partials (fixed size)
   NlkBuf sig;                     // nlk_dev_estimate_sigma: histograms, state, partials, keys (tu_sigma.hip)
   NlkBuf curve;                   // nlk_dev_estimate_noise_curve: the same per (channel, bin), block means and bins (tu_sigma.hip)

@@ -30,6 +30,10 @@
  *     OPM   "FSCALE1 DW1 TH1 FSCALE2 DW2 TH2": finest flow scale, flow data weight (lambda)
  *           and occlusion threshold of the forward / backward pass
  *           (default "1 0.25 0.75 1 0.25 0.75", script line 11)
+ *   --of tvl1|bm  in front of everything else, in all three tools (the scripts have no such thing): the flow estimator
+ *           of the run. tvl1 (default): the scripts' TV-L1. bm: block matching (nlk_dev_bm_flow) wherever
+ *           a flow is computed - the forward step, the backward pass, the lag-1 smoother's own flow; OPM's FSCALE and TH
+ *           apply, DW is ignored. The .flo and mask files hold the flow that was used.
  *
  * What the script does with four processes and ~10 image files per frame (reference:
  * scripts/nlkalman-seq.sh:30-150) happens here through the device C-ABI: per frame
@@ -384,7 +388,16 @@ static int finish_gt(const char *out, const double *d_sums, const double *d_ssim
 
 int main(int argc, const char **argv) {
   const int gt = NLK_SEQ_GT, lsmo = NLK_SEQ_LSMO;
-  int want_ssim = 0, lag1 = SEQ_LAG1_TVL1;
+  int want_ssim = 0, lag1 = SEQ_LAG1_TVL1, of = SEQ_OF_TVL1;
+  if (argc > 1 && !strcmp(argv[1], "--of")) { /* in front of every other option; the run's flow estimator */
+    if (argc < 3 || (of = seq_of_mode(argv[2])) < 0) {
+      fprintf(stderr, SEQ_OF_WANT, PROG, argc < 3 ? "" : argv[2]);
+      return 1;
+    }
+    argv[2] = argv[0];
+    argv += 2;
+    argc -= 2;
+  }
   if (lsmo && argc > 1 && !strcmp(argv[1], "--flow")) { /* the positional arguments follow its value */
     if (argc < 3 || !(lag1 = seq_lag1_mode(argv[2]))) {
       fprintf(stderr, "%s: --flow %s: want tvl1 or inv\n", PROG, argc < 3 ? "" : argv[2]);
@@ -402,13 +415,13 @@ int main(int argc, const char **argv) {
   }
   if (argc < 6) {
     if (gt)
-      fprintf(stderr, "usage: %s [--ssim] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
+      fprintf(stderr, "usage: %s [--of tvl1|bm] [--ssim] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
                       "  one-process equivalent of scripts/nlkalman-seq-gt.sh (see the header of main_seq.c)\n", argv[0]);
     else if (lsmo)
-      fprintf(stderr, "usage: %s [--flow tvl1|inv] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
+      fprintf(stderr, "usage: %s [--of tvl1|bm] [--flow tvl1|inv] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
                       "  one-process equivalent of scripts/nlkalman-lsmo-seq.sh (see the header of main_seq.c)\n", argv[0]);
     else
-      fprintf(stderr, "usage: %s SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]\n"
+      fprintf(stderr, "usage: %s [--of tvl1|bm] SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]\n"
                       "  one-process equivalent of scripts/nlkalman-seq.sh (see the header of main_seq.c)\n", argv[0]);
     return 1;
   }
@@ -561,7 +574,7 @@ int main(int argc, const char **argv) {
       seq_default_params(&f1, &f2, &s1, sig.sigma);
     }
     float *n1 = dev_frame(bytes), *n2 = dev_frame(bytes);
-    const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .f1 = &f1, .f2 = &f2,
+    const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .of = of, .sig = &sig, .f1 = &f1, .f2 = &f2,
                                   .fscale = fs1, .dw = dw1, .th = th1, .work = &W, .d_rgb = d_rgb,
                                   .prev_flt1 = t ? flt1 : NULL, .prev_flt2 = t ? flt2[t - 1] : NULL,
                                   .flt1 = n1, .flt2 = n2};
@@ -573,7 +586,7 @@ int main(int argc, const char **argv) {
     write_frame(path_of(out, OUTNAME("flt1"), i), n1, W.d_tmp, w, h, ch, SUM(0, t), SSIM(0, t), clean[t]);
     write_frame(path_of(out, OUTNAME("flt2"), i), n2, W.d_tmp, w, h, ch, SUM(1, t), SSIM(1, t), clean[t]);
     if (lsmo && smoothing && t > 0) { /* smooth the previous frame (script lines 87-108) */
-      const struct seq_lag1 lag = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = lag1,
+      const struct seq_lag1 lag = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = lag1, .of = of,
                                    .fscale = fs2, .dw = dw2, .th = th2, .work = &W, .d_fflow = W.d_fflow,
                                    .d_focc = W.d_focc, .flt2 = flt2[t - 1], .next = n2, .smo1 = d_lsm1};
       CHK(seq_lag1_step(&lag));
@@ -602,7 +615,7 @@ int main(int argc, const char **argv) {
   for (t = nframes - 2; t >= 0; --t) {
     const int i = ffr + t * stp;
     smo[t] = dev_frame(bytes);
-    const struct seq_lag1 back = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = SEQ_LAG1_TVL1,
+    const struct seq_lag1 back = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = SEQ_LAG1_TVL1, .of = of,
                                   .fscale = fs2, .dw = dw2, .th = th2, .work = &W, .d_fflow = W.d_flow,
                                   .d_focc = W.d_occ, .flt2 = flt2[t], .next = smo[t + 1], .smo1 = smo[t]};
     CHK(seq_lag1_step(&back));

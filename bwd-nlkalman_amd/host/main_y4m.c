@@ -15,6 +15,9 @@
  *                    written when frame t has been filtered; the last frame goes out as its flt2. tvl1: a second TV-L1
  *                    flow per frame, as the script; inv: the backward flow of frame t inverted (nlk_dev_flow_invert)
  *     --spm "..."    nlkalman-smo options (--s1_p ...), as nlkalman-seq's SPM
+ *     --of tvl1|bm   the flow estimator of the run, as nlkalman-seq's: tvl1 (default), or bm: block matching
+ *                    (nlk_dev_bm_flow) for the backward flow and for --smooth tvl1's own flow; --opm's FSCALE and TH
+ *                    apply, DW is ignored
  *     --frames N     stop after N frames
  *     --copy         convert to RGB and back only (no filter): the conversion path by itself
  *     --probe        no GPU, no output stream: parse IN, print one line
@@ -178,13 +181,14 @@ static int usage(void) {
           "usage: %s [options] SIG [IN [OUT]]     IN, OUT: a file or \"-\" (default: stdin, stdout)\n"
           "  SIG: a number | auto | vst | vst:A,B | nlf\n"
           "  --matrix 601|709|auto  --range limited|full|auto  --fpm \"...\"  --opm \"FSCALE DW TH [FSCALE2 DW2 TH2]\"\n"
-          "  --smooth tvl1|inv  --spm \"...\"  --frames N  --copy  --probe  -v       (see the header of main_y4m.c)\n", PROG);
+          "  --smooth tvl1|inv  --spm \"...\"  --frames N  --copy  --probe  -v       (see the header of main_y4m.c)\n"
+          "  --of tvl1|bm\n", PROG);
   return 1;
 }
 
 int main(int argc, const char **argv) {
   const char *matrix_s = "auto", *range_s = "auto", *fpm = "", *opm = "1 0.25 0.75", *pos[3] = {NULL, NULL, NULL};
-  const char *smooth_s = NULL, *spm = "";
+  const char *smooth_s = NULL, *spm = "", *of_s = "tvl1";
   long max_frames = -1;
   int copy = 0, want_probe = 0, verbose = 0, npos = 0;
   for (int i = 1; i < argc; ++i) {
@@ -196,6 +200,7 @@ int main(int argc, const char **argv) {
     else if (!strcmp(a, "--opm")) val = &opm;
     else if (!strcmp(a, "--smooth")) val = &smooth_s;
     else if (!strcmp(a, "--spm")) val = &spm;
+    else if (!strcmp(a, "--of")) val = &of_s;
     if (val) {
       if (++i >= argc) { fprintf(stderr, "%s: %s needs a value\n", PROG, a); return 1; }
       *val = argv[i];
@@ -232,6 +237,11 @@ int main(int argc, const char **argv) {
   int smooth = SEQ_LAG1_OFF;
   if (smooth_s && !(smooth = seq_lag1_mode(smooth_s))) {
     fprintf(stderr, "%s: --smooth %s: want tvl1 or inv\n", PROG, smooth_s);
+    return 1;
+  }
+  const int of = seq_of_mode(of_s);
+  if (of < 0) {
+    fprintf(stderr, SEQ_OF_WANT, PROG, of_s);
     return 1;
   }
   int matrix = 0, range = -1;
@@ -323,14 +333,14 @@ int main(int argc, const char **argv) {
         seq_default_params(&f1, &f2, &s1, sig.sigma);
       }
       const int cur = (int)(t & 1), prv = cur ^ 1;
-      const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .f1 = &f1, .f2 = &f2,
+      const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .of = of, .sig = &sig, .f1 = &f1, .f2 = &f2,
                                     .fscale = fs, .dw = dw, .th = th, .work = &W, .d_rgb = d_rgb,
                                     .prev_flt1 = t ? flt1[prv] : NULL, .prev_flt2 = t ? flt2[prv] : NULL,
                                     .flt1 = flt1[cur], .flt2 = flt2[cur]};
       CHK(seq_forward_step(&step));
       if (smooth) { /* frame t - 1 goes out smoothed, into its own buffer; frame t waits for the next one */
         if (t > 0) {
-          const struct seq_lag1 lag = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = smooth,
+          const struct seq_lag1 lag = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = smooth, .of = of,
                                        .fscale = fs2, .dw = dw2, .th = th2, .work = &W, .d_fflow = W.d_fflow,
                                        .d_focc = W.d_focc, .flt2 = flt2[prv], .next = flt2[cur], .smo1 = d_lsm1};
           CHK(seq_lag1_step(&lag));

@@ -163,6 +163,26 @@ static struct nlk_tvl1_params seq_flow_params(int w, int h, int fscale, float dw
   return of;
 }
 
+int seq_of_mode(const char *name) {
+  if (name && !strcmp(name, "tvl1")) return SEQ_OF_TVL1;
+  if (name && !strcmp(name, "bm")) return SEQ_OF_BM;
+  return -1;
+}
+
+/* the flow g0 -> g1 of a run's estimator: TV-L1 at this finest scale and data weight, or block matching at this finest
+ * scale (its other parameters are the defaults) */
+static int seq_flow(nlk_ctx *C, int of, float *d_flow, const float *d_g0, const float *d_g1, int w, int h, int fscale,
+                    float dw) {
+  if (of == SEQ_OF_BM) {
+    struct nlk_bmflow_params bm;
+    nlk_bmflow_default_params(&bm);
+    bm.fscale = fscale < 0 ? 0 : fscale;
+    return nlk_dev_bm_flow(C, d_flow, d_g0, d_g1, w, h, &bm);
+  }
+  const struct nlk_tvl1_params tv = seq_flow_params(w, h, fscale, dw);
+  return nlk_dev_tvl1_flow(C, d_flow, d_g0, d_g1, w, h, &tv, NULL);
+}
+
 /* the gray image of an opponent-space frame, as the flow tool reads its RGB file (d_tmp: of the frame's size) */
 static int gray_of_opp(nlk_ctx *C, float *d_gray, float *d_tmp, const float *d_opp, int w, int h, int ch) {
   TRY(nlk_d2d(C, d_tmp, d_opp, (size_t)w * h * ch * sizeof(float)));
@@ -196,10 +216,9 @@ int seq_forward_step(const struct seq_step *s) {
     return NLK_OK;
   }
   /* backward flow noisy_t -> flt2_{t-1}, occlusion mask (script lines 57-73) */
-  const struct nlk_tvl1_params of = seq_flow_params(w, h, s->fscale, s->dw);
   TRY(nlk_dev_gray(C, k->d_g0, s->d_rgb, w, h, ch));
   TRY(gray_of_opp(C, k->d_g1, k->d_tmp, s->prev_flt2, w, h, ch));
-  TRY(nlk_dev_tvl1_flow(C, k->d_flow, k->d_g0, k->d_g1, w, h, &of, NULL));
+  TRY(seq_flow(C, s->of, k->d_flow, k->d_g0, k->d_g1, w, h, s->fscale, s->dw));
   TRY(nlk_dev_occlusion_mask(C, k->d_occ, k->d_flow, w, h, s->th));
   TRY(nlk_dev_warp_bicubic(C, k->d_warp, s->prev_flt1, k->d_flow, k->d_occ, w, h, ch));
   TRY(nlk_dev_filter_frame(C, s->flt1, k->d_noisy, k->d_warp, NULL, w, h, ch, sigma, s->f1));
@@ -216,10 +235,9 @@ int seq_lag1_step(const struct seq_lag1 *s) {
     TRY(nlk_dev_flow_invert(C, s->d_fflow, k->d_flow, w, h, SEQ_LAG1_INVERT_STEPS));
   } else {
     /* forward flow flt2_i -> next, both as the flow tool reads their RGB files (script lines 90-96) */
-    const struct nlk_tvl1_params of = seq_flow_params(w, h, s->fscale, s->dw);
     TRY(gray_of_opp(C, k->d_g0, k->d_tmp, s->flt2, w, h, ch));
     TRY(gray_of_opp(C, k->d_g1, k->d_tmp, s->next, w, h, ch));
-    TRY(nlk_dev_tvl1_flow(C, s->d_fflow, k->d_g0, k->d_g1, w, h, &of, NULL));
+    TRY(seq_flow(C, s->of, s->d_fflow, k->d_g0, k->d_g1, w, h, s->fscale, s->dw));
   }
   TRY(nlk_dev_occlusion_mask(C, s->d_focc, s->d_fflow, w, h, s->th));
   TRY(nlk_dev_warp_bicubic(C, k->d_warp, s->next, s->d_fflow, s->d_focc, w, h, ch));

@@ -75,10 +75,20 @@ struct seq_work {
 int seq_work_alloc(nlk_ctx *ctx, struct seq_work *k, int w, int h, int ch, int with_smoother);
 void seq_work_free(nlk_ctx *ctx, struct seq_work *k);
 
+/* ---- the flow estimator of a run: every flow that a step computes comes from it */
+enum {
+  SEQ_OF_TVL1 = 0, /* the scripts': nlk_dev_tvl1_flow at OPM's FSCALE and DW */
+  SEQ_OF_BM        /* nlk_dev_bm_flow at OPM's FSCALE (its other parameters are the defaults; DW is ignored) */
+};
+/* "tvl1" | "bm" -> the estimator; anything else: -1 (the caller prints SEQ_OF_WANT under its own name) */
+int seq_of_mode(const char *name);
+#define SEQ_OF_WANT "%s: --of %s: want tvl1 or bm\n" /* (prog, text) */
+
 /* ---- one step of the forward recursion */
 struct seq_step {
   nlk_ctx *ctx;
   int w, h, ch;
+  int of;                    /* SEQ_OF_TVL1 | SEQ_OF_BM */
   const struct seq_sig *sig; /* resolved */
   const struct nlkalman_params *f1, *f2;
   int fscale;                /* backward flow: finest scale, data weight (lambda) and occlusion threshold */
@@ -89,8 +99,8 @@ struct seq_step {
   const float *prev_flt1, *prev_flt2; /* the previous frame's outputs (opponent space); both NULL on the first frame */
   float *flt1, *flt2;        /* out: this frame's (opponent space) */
 };
-/* variance stabilisation, rgb2opp, then FLT1 and FLT2: spatial on the first frame, afterwards gray -> TV-L1 flow
- * noisy_t -> flt2_{t-1} -> occlusion mask -> warp + FLT1 -> warp + FLT2 (scripts/nlkalman-seq.sh:39-101).
+/* variance stabilisation, rgb2opp, then FLT1 and FLT2: spatial on the first frame, afterwards gray -> flow (TV-L1, or
+ * under SEQ_OF_BM block matching) noisy_t -> flt2_{t-1} -> occlusion mask -> warp + FLT1 -> warp + FLT2 (scripts/nlkalman-seq.sh:39-101).
  * Asynchronous on the context's stream; returns the first failing call's code (nlk_last_error has the message). */
 int seq_forward_step(const struct seq_step *s);
 
@@ -100,7 +110,7 @@ int seq_forward_step(const struct seq_step *s);
  * flt2_i -> next it needs comes from one of two sources. */
 enum {
   SEQ_LAG1_OFF = 0,
-  SEQ_LAG1_TVL1,  /* the scripts': a TV-L1 flow of its own */
+  SEQ_LAG1_TVL1,  /* the scripts': a flow of its own (TV-L1, or under SEQ_OF_BM block matching) */
   SEQ_LAG1_INV    /* the inverse of the backward flow that the forward step of frame i + 1 left in work->d_flow */
 };
 /* fixed-point steps of nlk_dev_flow_invert in SEQ_LAG1_INV: the count at which the inverted flow was measured against
@@ -115,6 +125,7 @@ struct seq_lag1 {
   const struct seq_sig *sig; /* resolved */
   const struct nlkalman_params *s1;
   int mode;                  /* SEQ_LAG1_TVL1 | SEQ_LAG1_INV */
+  int of;                    /* SEQ_LAG1_TVL1: the estimator of that flow, SEQ_OF_TVL1 | SEQ_OF_BM */
   int fscale;                /* forward flow: finest scale and data weight (TVL1 only), occlusion threshold (both) */
   float dw, th;
   const struct seq_work *work; /* d_tmp, d_warp; TVL1: d_g0, d_g1; INV: d_flow, the backward flow next -> flt2_i */

@@ -57,14 +57,20 @@ class SequenceFilter:
     space, valid until the next push; None after the first push), .d_fflow / .d_focc the forward flow
     flt2_{t-1} -> flt2_t and its mask: "tvl1" computes that flow (its iteration counts go to .lag1_flow_iterations),
     "inv" inverts the backward flow of frame t (LAG1_INVERT_STEPS fixed-point steps). lag1_of_* / lag1_occ_th are the
-    second triple of OPM (default: the first). finish() gives the last frame's lsm1, its flt2."""
+    second triple of OPM (default: the first). finish() gives the last frame's lsm1, its flt2.
+    of="tvl1" | "bm": the flow estimator of the run, as the tools' --of. "bm": Context.bm_flow (block matching,
+    DESIGN.md §9) wherever a flow is computed - push(), smooth(), lag1="tvl1"'s own flow - at of_fscale / lag1_of_fscale;
+    of_lambda is ignored and flow_iterations / lag1_flow_iterations stay empty."""
 
     LAG1_INVERT_STEPS = 4   # SEQ_LAG1_INVERT_STEPS of host/seq_step.h
 
     def __init__(self, ctx, w, h, ch, sigma, f1=None, f2=None, s1=None, of_lambda=0.25, of_fscale=1,
                  occ_th=0.75, keep_history=True, lag1=None, lag1_of_lambda=None, lag1_of_fscale=None,
-                 lag1_occ_th=None):
+                 lag1_occ_th=None, of="tvl1"):
         pkg = _p()
+        if of not in ("tvl1", "bm"):
+            raise ValueError(f"SequenceFilter(of={of!r}): want 'tvl1' or 'bm'")
+        self.flow_estimator = of
         if lag1 not in (None, "tvl1", "inv"):
             raise ValueError(f"SequenceFilter(lag1={lag1!r}): want None, 'tvl1' or 'inv'")
         self.ctx, self.w, self.h, self.ch = ctx, w, h, ch
@@ -121,8 +127,16 @@ class SequenceFilter:
         c.d2d(self.d_rgb, d_to_opp, self.nbytes)
         c.opp2rgb(self.d_rgb, w, h, ch)
         c.gray(self.d_g1, self.d_rgb, w, h, ch)
-        self.flow_iterations.append(c.tvl1_flow(self.d_flow, self.d_g0, self.d_g1, w, h, self.of))
+        self._flow(self.d_flow, self.of, self.flow_iterations)
         c.occlusion_mask(self.d_occ, self.d_flow, w, h, self.occ_th)
+
+    def _flow(self, d_flow, of, iterations):
+        """the flow d_g0 -> d_g1 of the run's estimator (seq_flow of host/seq_step.c)"""
+        c, w, h = self.ctx, self.w, self.h
+        if self.flow_estimator == "bm":
+            c.bm_flow(d_flow, self.d_g0, self.d_g1, w, h, fscale=max(of.fscale, 0))
+        else:
+            iterations.append(c.tvl1_flow(d_flow, self.d_g0, self.d_g1, w, h, of))
 
     def push(self, d_noisy_rgb):
         """Next noisy frame (device pointer, HWC RGB or gray, not modified). Afterwards
@@ -191,7 +205,7 @@ class SequenceFilter:
                 c.d2d(self.d_rgb, d_opp, self.nbytes)
                 c.opp2rgb(self.d_rgb, w, h, ch)
                 c.gray(d_gray, self.d_rgb, w, h, ch)
-            self.lag1_flow_iterations.append(c.tvl1_flow(self.d_fflow, self.d_g0, self.d_g1, w, h, self.of2))
+            self._flow(self.d_fflow, self.of2, self.lag1_flow_iterations)
         c.occlusion_mask(self.d_focc, self.d_fflow, w, h, self.occ_th2)
         c.warp_bicubic(self.d_warp, d_cur, self.d_fflow, self.d_focc, w, h, ch)
         if self.lsm1 is None:

@@ -60,7 +60,13 @@ def noise_affine(clean, ab, seed):
 def clean_frame(w, h, ch, t=0):
     """Sinusoids + checker blocks + a few hard edges, values in 0..255."""
     y, x = np.mgrid[0:h, 0:w].astype(np.float64)
-    x = x + 2.0 * t
+    return clean_scene(x + 2.0 * t, y, ch)
+
+
+def clean_scene(x, y, ch, rows=None):
+    """clean_frame's pattern at the scene coordinates (x, y) of every pixel (float64 arrays): what a camera that has
+    moved sees. rows: the pixels' own row numbers, which the green cast follows (default: y)."""
+    rows = y if rows is None else rows
     im = (128.0 + 50.0 * np.sin(x / 9.0) * np.cos(y / 13.0)
           + 30.0 * np.sin((x + 2.0 * y) / 37.0)
           + 35.0 * ((((x // 24) + (y // 24)) % 2) - 0.5)
@@ -69,7 +75,7 @@ def clean_frame(w, h, ch, t=0):
     gains = np.array([1.0, 0.85, 0.7])[:ch] if ch <= 3 else np.ones(ch)
     out = im[:, :, None] * gains[None, None, :]
     if ch == 3:
-        out[:, :, 1] = np.clip(out[:, :, 1] + 20.0 * np.cos(y / 21.0), 0, 255)
+        out[:, :, 1] = np.clip(out[:, :, 1] + 20.0 * np.cos(rows / 21.0), 0, 255)
         out[:, :, 2] = np.clip(out[:, :, 2] + 15.0 * np.sin(x / 17.0), 0, 255)
     return out.astype(np.float32)
 

@@ -23,6 +23,7 @@
  *   nlk_dev_tvl1_flow                   lib/tvl1flow/tvl1flow_lib.c:345-474
  *                                       (Dual_TVL1_optic_flow_multiscale)
  *   nlk_tvl1_default_params / _scales   lib/tvl1flow/main.c:26-35, 152-157
+ *   nlk_dev_bm_flow                     (none: hierarchical block matching, stated by tests/bmflow_ref.py)
  *   nlk_dev_gray                        lib/iio/iio.c:1048-1056 (what the flow tool's
  *                                       reader does to a colour image)
  *   nlk_dev_occlusion_mask              scripts/nlkalman-seq.sh:70-73 (plambda)
@@ -181,6 +182,27 @@ int nlk_dev_occlusion_mask(nlk_ctx *ctx, float *mask, const float *flow, int w, 
  * asynchronous on the context's stream. NLK_EINVAL for w or h < 1, iters outside 0..16, a NULL pointer or
  * inv == flow (the arrays must not overlap); the context keeps working after a refused call. */
 int nlk_dev_flow_invert(nlk_ctx *ctx, float *inv, const float *flow, int w, int h, int iters);
+/* A second, much cheaper flow estimator for consumers that tolerate its error (the sequence recursion: the matcher
+ * searches +-5 px after the warp, the Kalman gain absorbs misalignment): hierarchical block matching.
+ * Same images, layout and direction as nlk_dev_tvl1_flow: I1(q + flow(q)) ~ I0(q). Stated once, in numpy, by
+ * tests/bmflow_ref.py; for finite images the kernels give its bits (float32, every operation rounded by itself), the
+ * same on every run. A pyramid of 2 x 2 box means, levels added while min(w, h) / 2 >= min_side (below 8: 8); from the
+ * coarsest level to level min(fscale, levels): 8 x 8 blocks at stride 4, each predicted by the coarser level's flow,
+ * matched by SSD over [-radius, radius]^2 around the prediction with a parabola per axis for the sub-pel part, a 3 x 3
+ * median over the block grid, bilinear interpolation between the block centres; x2 bilinear upsampling from that level
+ * to level 0. An image with a side below 8 has the flow 0. */
+struct nlk_bmflow_params {
+  int fscale;   /* finest level that is matched; finer ones get the upsampled flow (1) */
+  int radius;   /* search radius around the prediction, 1..3 (2) */
+  int min_side; /* no pyramid level with a side below this (16) */
+};
+void nlk_bmflow_default_params(struct nlk_bmflow_params *p);
+/* prms = NULL: the defaults. Asynchronous on the context's stream; its scratch belongs to the context, is sized for
+ * every fscale and min_side at once (about 1.7 floats per pixel) and so grows only with the image size. No input, non-finite ones included, makes a kernel read outside an array; what a non-finite
+ * image gives is unspecified. NLK_EINVAL for a NULL image, w or h < 1, radius outside 1..3 or fscale < 0; NLK_EUNSUP
+ * for h > 262137; the context keeps working after a refused call. */
+int nlk_dev_bm_flow(nlk_ctx *ctx, float *flow, const float *I0, const float *I1, int w, int h,
+                    const struct nlk_bmflow_params *prms);
 
 /* ---- multiscale wrapper (reference: lib/multiscale/multiscaler.cpp:21-107).
  * nlk_dev_image_dct: in-place whole-image DCT of an HWC image — forward = FFTW REDFT10 in both
