@@ -43,6 +43,7 @@ HIP_SYMBOLS = [
     "nlk_nlf_build", "nlk_dev_nlf_forward", "nlk_dev_nlf_inverse",
     "nlk_yuv_format_from_tag", "nlk_yuv_frame_bytes", "nlk_dev_yuv_to_rgb", "nlk_dev_rgb_to_yuv",
     "nlk_dev_flow_invert", "nlk_bmflow_default_params", "nlk_dev_bm_flow",
+    "nlk_dev_probe_add", "nlk_dev_sure_terms", "nlk_sure_mse",
 ]
 API_SYMBOLS = [
     "rgb2opp", "opp2rgb", "warp_bicubic", "nlkalman_default_params",
@@ -211,6 +212,10 @@ def hip():
         L.nlk_dev_awgn.argtypes = [vp, fp, fp, C.c_size_t, f, C.c_uint32]
         L.nlk_dev_sqdiff_sum.argtypes = [vp, vp, fp, fp, C.c_size_t]
         L.nlk_dev_ssim.argtypes = [vp, vp, fp, fp, fp, i, i, i, f]
+        L.nlk_dev_probe_add.argtypes = [vp, fp, fp, C.c_size_t, f, C.c_uint64]
+        L.nlk_dev_sure_terms.argtypes = [vp, vp, vp, fp, fp, fp, i, i, i, i, C.c_uint64]
+        L.nlk_sure_mse.argtypes = [C.c_double] * 5
+        L.nlk_sure_mse.restype = C.c_double
         L.nlk_sigma_default_params.argtypes = [C.POINTER(SigmaParams)]
         L.nlk_sigma_default_params.restype = None
         L.nlk_dev_estimate_sigma.argtypes = [vp, fp, vp, fp, i, i, i, C.POINTER(SigmaParams)]
@@ -382,6 +387,11 @@ def nlf_build(bins, lo=0.0, hi=256.0, rho=NLF_RHO):
     if rc:
         raise ValueError(f"nlf_build: refused (rc={rc}): ch = {b.shape[0]}, nbins = {b.shape[1]}, lo = {lo}, hi = {hi}, rho = {rho}")
     return t
+
+
+def sure_mse(R, D, n, sigma, eps):
+    """Monte-Carlo SURE from its two sums over n samples (nlk_sure_mse): R / n - sigma^2 + 2 sigma^2 D / (eps n)."""
+    return float(hip().nlk_sure_mse(float(R), float(D), float(n), float(sigma), float(eps)))
 
 
 def default_params(sigma, mode, **over):
@@ -664,6 +674,32 @@ class Context:
             if d_map is not None:
                 self.free(d_map)
         return (float(s[0]), s[1:].copy(), smap) if want_map else (float(s[0]), s[1:].copy())
+
+    # ---- the error estimate without clean frames (include/nlk_hip.h: nlk_dev_probe_add, nlk_dev_sure_terms)
+    def probe_add(self, d_out, d_in, n, eps, seed):
+        """d_out[i] = d_in[i] + (b_i > 0 ? eps : -eps) for i < n, b the signs of `seed` (d_out may be d_in)."""
+        self._chk(self.L.nlk_dev_probe_add(self.h, d_out, d_in, n, float(eps), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def sure_terms_dev(self, d_total, d_blocks, d_y, d_f, d_fp, w, h, ch, block=16, seed=0):
+        """d_total[2 c], d_total[2 c + 1] = R_c, D_c of the device images y, f = filter(y), fp = filter(y + eps b)
+        (device doubles); d_blocks: None, or the [nby][nbx][ch][2] map of the same sums per tile. Not synchronised."""
+        self._chk(self.L.nlk_dev_sure_terms(self.h, d_total, d_blocks, d_y, d_f, d_fp, w, h, ch, block,
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def sure_terms(self, d_y, d_f, d_fp, w, h, ch, block=16, seed=0, want_blocks=False):
+        """totals [ch][2] float64 = (R_c, D_c); with want_blocks also the map [nby][nbx][ch][2]. Waits for the device."""
+        nby, nbx = -(-max(h, 1) // max(block, 1)), -(-max(w, 1) // max(block, 1))
+        d = self.alloc(16 * max(ch, 1))
+        d_map = self.alloc(16 * max(ch, 1) * nby * nbx) if want_blocks else None
+        try:
+            self.sure_terms_dev(d, d_map, d_y, d_f, d_fp, w, h, ch, block, seed)
+            tot = self.download(d, (ch, 2), np.float64)
+            blocks = self.download(d_map, (nby, nbx, ch, 2), np.float64) if want_blocks else None
+        finally:
+            self.free(d)
+            if d_map is not None:
+                self.free(d_map)
+        return (tot, blocks) if want_blocks else tot
 
     # ---- the noise level of an image (include/nlk_hip.h: nlk_dev_estimate_sigma)
     def estimate_sigma(self, d_img, w, h, ch, **params):

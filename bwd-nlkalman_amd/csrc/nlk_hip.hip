@@ -188,7 +188,7 @@ void nlk_ctx_destroy(nlk_ctx* c) {
   hipStreamSynchronize(c->stream);
   if (c->aux_stream) hipStreamSynchronize(c->aux_stream);
   Buf* bufs[] = {&c->planes, &c->rowok, &c->vmap, &c->topk,
-                 &c->tinfo, &c->gcoords, &c->marks, &c->active, &c->acc, &c->tabs, &c->wide, &c->tv, &c->bm, &c->skew, &c->chase, &c->ms, &c->lz3, &c->sqd, &c->sig, &c->curve, &c->ssim, &c->nlf,
+                 &c->tinfo, &c->gcoords, &c->marks, &c->active, &c->acc, &c->tabs, &c->wide, &c->tv, &c->bm, &c->skew, &c->chase, &c->ms, &c->lz3, &c->sqd, &c->sig, &c->curve, &c->ssim, &c->sure, &c->nlf,
                  &c->slab, &c->tflag, &c->hw_cur, &c->hw_prev, &c->hw_basic, &c->hw_out};
   for (Buf* b : bufs)
     if (b->p) hipFree(b->base ? b->base : b->p);

@@ -98,6 +98,7 @@ struct nlk_ctx {
   NlkBuf sig;                     // nlk_dev_estimate_sigma: histograms, state, partials, keys (tu_sigma.hip)
   NlkBuf curve;                   // nlk_dev_estimate_noise_curve: the same per (channel, bin), block means and bins (tu_sigma.hip)
   NlkBuf ssim;                   // nlk_dev_ssim: one partial per (channel, tile) (tu_ssim.hip)
+  NlkBuf sure;                    // nlk_dev_sure_terms without a map: the sums of every tile (tu_sure.hip)
   NlkBuf nlf;                     // nlk_dev_nlf_forward / _inverse: the device copy of the last table given ...
   float* nlf_host = nullptr;      // ... and what it holds (malloc), to tell a new table from it (tu_nlf.hip)
   NlkBuf slab, tflag;             // deterministic aggregation: per-tile accumulator slabs + "written" flags (k_gather.h)

@@ -34,6 +34,14 @@
  *           of the run. tvl1 (default): the scripts' TV-L1. bm: block matching (nlk_dev_bm_flow) wherever
  *           a flow is computed - the forward step, the backward pass, the lag-1 smoother's own flow; OPM's FSCALE and TH
  *           apply, DW is ignored. The .flo and mask files hold the flow that was used.
+ *   --sure  after --of, in front of the rest, in all three tools (the scripts have no such thing): the error of every
+ *           flt1 / flt2 frame is estimated without clean frames by Monte-Carlo SURE (seq_sure_step, host/seq_step.h;
+ *           DESIGN.md §9): one more FLT1 and FLT2 per frame, on the noisy frame plus a probe of +-eps. OUT/measures-sure
+ *           gets, per pass, "F1 I MSE_hat PSNR_hat R/N div" for every frame I and "F1 total ..." (finish_sure), each
+ *           value "%.9g", PSNR at 255; the gt tool adds a last stdout line "sure T_F1 T_F2". Under SIG = vst | nlf the
+ *           estimate is in the stabilised domain, at the run's sigma. The smoother's outputs are not estimated.
+ *           NLK_SURE_EPS (eps / sigma, default 0.05) and NLK_SURE_SEED override the probe. Without the flag nothing of
+ *           this happens: the same launches, allocations, files and stdout as before.
  *
  * What the script does with four processes and ~10 image files per frame (reference:
  * scripts/nlkalman-seq.sh:30-150) happens here through the device C-ABI: per frame
@@ -386,6 +394,46 @@ static int finish_gt(const char *out, const double *d_sums, const double *d_ssim
   return 0;
 }
 
+/* ---- --sure: the error estimate of every forward step without clean frames (seq_sure_step, host/seq_step.h) */
+static struct {
+  int on;
+  struct seq_sure u;
+  double *d_terms; /* [frame][pass: flt1, flt2][ch][2] device doubles, downloaded once at the end */
+  int nframes, ffr, stp, w, h, ch;
+} S;
+
+/* OUT/measures-sure, every value "%.9g": per pass "F1 I MSE_hat PSNR_hat R/N div" for every frame I, then
+ * "F1 total ..." = the means of MSE_hat, R/N and div over the frames and the PSNR of that mean MSE_hat (at 255); the gt
+ * tool adds a last stdout line "sure T_F1 T_F2", the two mean MSE_hat. rc: what the run returns without --sure */
+static int finish_sure(const char *out, int rc) {
+  if (!S.on || rc) return rc;
+  static const char *label[2] = {"F1", "F2"};
+  const size_t per = (size_t)4 * S.ch;
+  double *terms = malloc(sizeof(double) * per * S.nframes), tot[2];
+  CHK(nlk_d2h(C, terms, S.d_terms, sizeof(double) * per * S.nframes));
+  char *path = path_of(out, "measures-sure", 0);
+  FILE *f = fopen(path, "w");
+  if (!f) { perror(path); free(path); return 1; }
+  for (int p = 0; p < 2; ++p) {
+    double m = 0.0, r = 0.0, d = 0.0;
+    for (int t = 0; t < S.nframes; ++t) {
+      const struct seq_sure_est e =
+          seq_sure_estimate(terms + t * per + (size_t)p * 2 * S.ch, S.w, S.h, S.ch, sig.sigma, S.u.eps_rel);
+      fprintf(f, "%s %d %.9g %.9g %.9g %.9g\n", label[p], S.ffr + t * S.stp, e.mse, e.psnr, e.resid, e.div);
+      m += e.mse; r += e.resid; d += e.div;
+    }
+    tot[p] = m / S.nframes;
+    fprintf(f, "%s total %.9g %.9g %.9g %.9g\n", label[p], tot[p], 10.0 * log10(255.0 * 255.0 / tot[p]), r / S.nframes,
+            d / S.nframes);
+  }
+  free(terms);
+  const int bad = fclose(f) != 0;
+  if (bad) perror(path);
+  free(path);
+  if (!bad && NLK_SEQ_GT) printf("sure %.9g %.9g\n", tot[0], tot[1]);
+  return bad;
+}
+
 int main(int argc, const char **argv) {
   const int gt = NLK_SEQ_GT, lsmo = NLK_SEQ_LSMO;
   int want_ssim = 0, lag1 = SEQ_LAG1_TVL1, of = SEQ_OF_TVL1;
@@ -397,6 +445,12 @@ int main(int argc, const char **argv) {
     argv[2] = argv[0];
     argv += 2;
     argc -= 2;
+  }
+  if (argc > 1 && !strcmp(argv[1], "--sure")) { /* after --of, in front of the rest */
+    S.on = 1;
+    argv[1] = argv[0];
+    ++argv;
+    --argc;
   }
   if (lsmo && argc > 1 && !strcmp(argv[1], "--flow")) { /* the positional arguments follow its value */
     if (argc < 3 || !(lag1 = seq_lag1_mode(argv[2]))) {
@@ -415,14 +469,20 @@ int main(int argc, const char **argv) {
   }
   if (argc < 6) {
     if (gt)
-      fprintf(stderr, "usage: %s [--of tvl1|bm] [--ssim] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
-                      "  one-process equivalent of scripts/nlkalman-seq-gt.sh (see the header of main_seq.c)\n", argv[0]);
+      fprintf(stderr, "usage: %s [--of tvl1|bm] [--sure] [--ssim] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
+                      "  one-process equivalent of scripts/nlkalman-seq-gt.sh (see the header of main_seq.c)\n"
+                      "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
+                      "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
     else if (lsmo)
-      fprintf(stderr, "usage: %s [--of tvl1|bm] [--flow tvl1|inv] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
-                      "  one-process equivalent of scripts/nlkalman-lsmo-seq.sh (see the header of main_seq.c)\n", argv[0]);
+      fprintf(stderr, "usage: %s [--of tvl1|bm] [--sure] [--flow tvl1|inv] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
+                      "  one-process equivalent of scripts/nlkalman-lsmo-seq.sh (see the header of main_seq.c)\n"
+                      "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
+                      "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
     else
-      fprintf(stderr, "usage: %s [--of tvl1|bm] SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]\n"
-                      "  one-process equivalent of scripts/nlkalman-seq.sh (see the header of main_seq.c)\n", argv[0]);
+      fprintf(stderr, "usage: %s [--of tvl1|bm] [--sure] SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]\n"
+                      "  one-process equivalent of scripts/nlkalman-seq.sh (see the header of main_seq.c)\n"
+                      "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
+                      "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
     return 1;
   }
   const char *seq = argv[1], *out = argv[5];
@@ -522,6 +582,13 @@ int main(int argc, const char **argv) {
       d_rgb = dev_frame(bytes);
       CHK(seq_work_alloc(C, &W, w, h, ch, lsmo && smoothing));
       if (lsmo && smoothing) d_lsm1 = dev_frame(bytes);
+      if (S.on) {
+        void *d = NULL;
+        CHK(seq_sure_alloc(C, &S.u, w, h, ch, 0));
+        CHK(nlk_dev_alloc(C, &d, sizeof(double) * 4 * ch * nframes));
+        S.d_terms = (double *)d;
+        S.nframes = nframes; S.ffr = ffr; S.stp = stp; S.w = w; S.h = h; S.ch = ch;
+      }
       pool_init(bytes > (size_t)w * h * 8 ? bytes : (size_t)w * h * 8);
       if (Q.nthreads > 0) {
         void *hp = NULL;
@@ -579,6 +646,7 @@ int main(int argc, const char **argv) {
                                   .prev_flt1 = t ? flt1 : NULL, .prev_flt2 = t ? flt2[t - 1] : NULL,
                                   .flt1 = n1, .flt2 = n2};
     CHK(seq_forward_step(&step));
+    if (S.on) CHK(seq_sure_step(&step, &S.u, t, S.d_terms + (size_t)t * 4 * ch));
     if (t > 0) { /* the flow and its mask (script lines 57-73) */
       write_dev(path_of(out, lsmo ? "bflo-%03d.flo" : "bflo1-%03d.flo", i), W.d_flow, w, h, 2);
       write_dev(path_of(out, lsmo ? "bocc-%03d.png" : "bocc1-%03d.png", i), W.d_occ, w, h, 1);
@@ -603,9 +671,10 @@ int main(int argc, const char **argv) {
   }
   if (lsmo) { /* the last frame's lsm1 is its flt2 (script lines 112-116) */
     if (smoothing) write_frame(path_of(out, "lsm1-%03d.tif", lfr), flt2[nframes - 1], W.d_tmp, w, h, ch, NULL, NULL, NULL);
-    return wq_finish();
+    return finish_sure(out, wq_finish());
   }
-  if (!smoothing) return gt ? finish_gt(out, d_sums, d_ssims, 2, nframes, ch, (size_t)w * h * ch) : wq_finish(); /* script line 113 */
+  if (!smoothing) /* script line 113 */
+    return finish_sure(out, gt ? finish_gt(out, d_sums, d_ssims, 2, nframes, ch, (size_t)w * h * ch) : wq_finish());
 
   /* ---- backward pass (script lines 117-150) */
   float **smo = calloc(nframes, sizeof(float *));
@@ -624,5 +693,5 @@ int main(int argc, const char **argv) {
     write_frame(path_of(out, OUTNAME("smo1"), i), smo[t], W.d_tmp, w, h, ch, SUM(2, t), SSIM(2, t), clean[t]);
     if (verbose) printf("frame %d smoothed\n", i);
   }
-  return gt ? finish_gt(out, d_sums, d_ssims, 3, nframes, ch, (size_t)w * h * ch) : wq_finish();
+  return finish_sure(out, gt ? finish_gt(out, d_sums, d_ssims, 3, nframes, ch, (size_t)w * h * ch) : wq_finish());
 }

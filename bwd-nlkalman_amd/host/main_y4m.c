@@ -18,6 +18,12 @@
  *     --of tvl1|bm   the flow estimator of the run, as nlkalman-seq's: tvl1 (default), or bm: block matching
  *                    (nlk_dev_bm_flow) for the backward flow and for --smooth tvl1's own flow; --opm's FSCALE and TH
  *                    apply, DW is ignored
+ *     --sure         the error of every flt2 frame estimated without clean frames by Monte-Carlo SURE (seq_sure_step,
+ *                    host/seq_step.h): one more FLT1 and FLT2 per frame. One stderr line per frame,
+ *                    "sure T MSE_hat PSNR_hat R/N div" (T from 1, each value "%.9g", PSNR at 255), and at the end
+ *                    "sure total ..." with the means over the frames; the output stream is what it is without the
+ *                    option. Under SIG = vst | nlf the estimate is in the stabilised domain, at the run's sigma; with
+ *                    --smooth it is still flt2's. NLK_SURE_EPS, NLK_SURE_SEED: as nlkalman-seq's.
  *     --frames N     stop after N frames
  *     --copy         convert to RGB and back only (no filter): the conversion path by itself
  *     --probe        no GPU, no output stream: parse IN, print one line
@@ -182,7 +188,9 @@ static int usage(void) {
           "  SIG: a number | auto | vst | vst:A,B | nlf\n"
           "  --matrix 601|709|auto  --range limited|full|auto  --fpm \"...\"  --opm \"FSCALE DW TH [FSCALE2 DW2 TH2]\"\n"
           "  --smooth tvl1|inv  --spm \"...\"  --frames N  --copy  --probe  -v       (see the header of main_y4m.c)\n"
-          "  --of tvl1|bm\n", PROG);
+          "  --of tvl1|bm\n"
+          "  --sure  one stderr line per frame, \"sure T MSE_hat PSNR_hat R/N div\": flt2's error estimated without clean\n"
+          "          frames (Monte-Carlo SURE; under SIG = vst | nlf in the stabilised domain, at the run's sigma)\n", PROG);
   return 1;
 }
 
@@ -190,7 +198,7 @@ int main(int argc, const char **argv) {
   const char *matrix_s = "auto", *range_s = "auto", *fpm = "", *opm = "1 0.25 0.75", *pos[3] = {NULL, NULL, NULL};
   const char *smooth_s = NULL, *spm = "", *of_s = "tvl1";
   long max_frames = -1;
-  int copy = 0, want_probe = 0, verbose = 0, npos = 0;
+  int copy = 0, want_probe = 0, verbose = 0, npos = 0, want_sure = 0;
   for (int i = 1; i < argc; ++i) {
     const char *a = argv[i];
     const char **val = NULL;
@@ -212,6 +220,7 @@ int main(int argc, const char **argv) {
       }
     } else if (!strcmp(a, "--copy")) copy = 1;
     else if (!strcmp(a, "--probe")) want_probe = 1;
+    else if (!strcmp(a, "--sure")) want_sure = 1;
     else if (!strcmp(a, "-v")) verbose = 1;
     else if (!strcmp(a, "-h") || !strcmp(a, "--help")) { usage(); return 0; }
     else if (a[0] == '-' && a[1] && !(npos == 0 && (a[1] == '.' || (a[1] >= '0' && a[1] <= '9')))) {
@@ -317,6 +326,15 @@ int main(int argc, const char **argv) {
   CHK(nlk_dev_alloc(C, &d_yuv, hd.frame_bytes));
   for (int i = 0; i < (smooth ? 6 : 5); ++i) CHK(nlk_dev_alloc(C, &fr[i], bytes));
   float *d_rgb = fr[0], *flt1[2] = {fr[1], fr[2]}, *flt2[2] = {fr[3], fr[4]}, *d_lsm1 = fr[5];
+  /* --sure: the probe's images, the terms of one frame (flt1's, then flt2's) and the sums of the lines printed */
+  struct seq_sure U = {0};
+  void *d_terms = NULL;
+  double sure_sum[3] = {0.0, 0.0, 0.0};
+  if (copy) want_sure = 0; /* (nothing is filtered) */
+  if (want_sure) {
+    CHK(seq_sure_alloc(C, &U, w, h, ch, 0));
+    CHK(nlk_dev_alloc(C, &d_terms, sizeof(double) * 4 * ch));
+  }
 
   long t = 0;
   int failed = 0;
@@ -338,6 +356,14 @@ int main(int argc, const char **argv) {
                                     .prev_flt1 = t ? flt1[prv] : NULL, .prev_flt2 = t ? flt2[prv] : NULL,
                                     .flt1 = flt1[cur], .flt2 = flt2[cur]};
       CHK(seq_forward_step(&step));
+      if (want_sure) {
+        double terms[4 * SEQ_SIG_MAX_CH];
+        CHK(seq_sure_step(&step, &U, t, (double *)d_terms));
+        CHK(nlk_d2h(C, terms, d_terms, sizeof(double) * 4 * ch));
+        const struct seq_sure_est e = seq_sure_estimate(terms + 2 * ch, w, h, ch, sig.sigma, U.eps_rel);
+        fprintf(stderr, "sure %ld %.9g %.9g %.9g %.9g\n", t + 1, e.mse, e.psnr, e.resid, e.div);
+        sure_sum[0] += e.mse; sure_sum[1] += e.resid; sure_sum[2] += e.div;
+      }
       if (smooth) { /* frame t - 1 goes out smoothed, into its own buffer; frame t waits for the next one */
         if (t > 0) {
           const struct seq_lag1 lag = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = smooth, .of = of,
@@ -374,12 +400,19 @@ int main(int argc, const char **argv) {
     pthread_join(th_w, NULL);
     /* after an early `break` the reader may still wait for a slot: the process ends without joining it */
   }
+  if (want_sure && t > 0 && !failed)
+    fprintf(stderr, "sure total %.9g %.9g %.9g %.9g\n", sure_sum[0] / t, 10.0 * log10(255.0 * 255.0 * t / sure_sum[0]),
+            sure_sum[1] / t, sure_sum[2] / t);
   if (fflush(out) || (out != stdout && fclose(out))) { fprintf(stderr, "%s: write error\n", PROG); failed = 1; }
   if (G.write_failed) { fprintf(stderr, "%s: %s\n", PROG, G.write_err); failed = 1; }
   if (G.read_failed) { fprintf(stderr, "%s: frame %ld: %s\n", PROG, t + 1, G.read_err); failed = 1; }
   nlk_dev_free(C, d_yuv);
   for (int i = 0; i < 6; ++i)
     if (fr[i]) nlk_dev_free(C, fr[i]);
+  if (want_sure) {
+    seq_sure_free(C, &U);
+    nlk_dev_free(C, d_terms);
+  }
   seq_work_free(C, &W);
   return failed;
 }

@@ -1,6 +1,7 @@
 /* seq_step.c — see seq_step.h */
 #include "seq_step.h"
 
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -225,6 +226,66 @@ int seq_forward_step(const struct seq_step *s) {
   TRY(nlk_dev_warp_bicubic(C, k->d_warp, s->prev_flt2, k->d_flow, k->d_occ, w, h, ch));
   TRY(nlk_dev_filter_frame(C, s->flt2, k->d_noisy, k->d_warp, s->flt1, w, h, ch, sigma, s->f2));
   return NLK_OK;
+}
+
+int seq_sure_alloc(nlk_ctx *C, struct seq_sure *u, int w, int h, int ch, int with_map) {
+  const size_t bytes = (size_t)w * h * ch * sizeof(float);
+  memset(u, 0, sizeof *u);
+  u->eps_rel = SEQ_SURE_EPS_REL;
+  u->block = SEQ_SURE_BLOCK;
+  const char *e = getenv("NLK_SURE_EPS");
+  if (e && atof(e) > 0.0) u->eps_rel = (float)atof(e);
+  if ((e = getenv("NLK_SURE_SEED"))) u->seed = strtoull(e, NULL, 0);
+  float **want[] = {&u->d_probe, &u->d_flt1, &u->d_flt2};
+  for (int i = 0; i < 3; ++i) {
+    void *d = NULL;
+    TRY(nlk_dev_alloc(C, &d, bytes));
+    *want[i] = (float *)d;
+  }
+  if (with_map) {
+    const size_t nbx = (w + u->block - 1) / u->block, nby = (h + u->block - 1) / u->block;
+    void *d = NULL;
+    TRY(nlk_dev_alloc(C, &d, nbx * nby * ch * 2 * sizeof(double)));
+    u->d_blocks = (double *)d;
+  }
+  return NLK_OK;
+}
+
+void seq_sure_free(nlk_ctx *C, struct seq_sure *u) {
+  void *all[] = {u->d_probe, u->d_flt1, u->d_flt2, u->d_blocks};
+  for (int i = 0; i < 4; ++i)
+    if (all[i]) nlk_dev_free(C, all[i]);
+  u->d_probe = u->d_flt1 = u->d_flt2 = NULL;
+  u->d_blocks = NULL;
+}
+
+int seq_sure_step(const struct seq_step *s, const struct seq_sure *u, long t, double *d_slot) {
+  nlk_ctx *C = s->ctx;
+  const struct seq_work *k = s->work;
+  const int w = s->w, h = s->h, ch = s->ch;
+  const float sigma = s->sig->sigma;
+  const uint64_t seed = u->seed + (uint64_t)t * SEQ_SURE_FRAME_STEP;
+  TRY(nlk_dev_probe_add(C, u->d_probe, k->d_noisy, (size_t)w * h * ch, u->eps_rel * sigma, seed));
+  const int temporal = s->prev_flt2 != NULL;
+  if (temporal) TRY(nlk_dev_warp_bicubic(C, k->d_warp, s->prev_flt1, k->d_flow, k->d_occ, w, h, ch));
+  TRY(nlk_dev_filter_frame(C, u->d_flt1, u->d_probe, temporal ? k->d_warp : NULL, NULL, w, h, ch, sigma, s->f1));
+  if (temporal) TRY(nlk_dev_warp_bicubic(C, k->d_warp, s->prev_flt2, k->d_flow, k->d_occ, w, h, ch));
+  TRY(nlk_dev_filter_frame(C, u->d_flt2, u->d_probe, temporal ? k->d_warp : NULL, u->d_flt1, w, h, ch, sigma, s->f2));
+  TRY(nlk_dev_sure_terms(C, d_slot, NULL, k->d_noisy, s->flt1, u->d_flt1, w, h, ch, u->block, seed));
+  TRY(nlk_dev_sure_terms(C, d_slot + 2 * ch, u->d_blocks, k->d_noisy, s->flt2, u->d_flt2, w, h, ch, u->block, seed));
+  return NLK_OK;
+}
+
+struct seq_sure_est seq_sure_estimate(const double *terms, int w, int h, int ch, float sigma, float eps_rel) {
+  double R = 0.0, D = 0.0;
+  for (int c = 0; c < ch; ++c) { R += terms[2 * c]; D += terms[2 * c + 1]; }
+  const double n = (double)w * h * ch, eps = (double)(eps_rel * sigma);
+  struct seq_sure_est e;
+  e.mse = nlk_sure_mse(R, D, n, (double)sigma, eps);
+  e.psnr = 10.0 * log10(255.0 * 255.0 / e.mse); /* (NaN for an estimate that is not positive) */
+  e.resid = R / n;
+  e.div = D / (eps * n);
+  return e;
 }
 
 int seq_lag1_step(const struct seq_lag1 *s) {

@@ -104,6 +104,35 @@ struct seq_step {
  * Asynchronous on the context's stream; returns the first failing call's code (nlk_last_error has the message). */
 int seq_forward_step(const struct seq_step *s);
 
+/* ---- the error estimate of a forward step without clean frames: Monte-Carlo SURE (include/nlk_hip.h: nlk_dev_probe_add,
+ * nlk_dev_sure_terms). The noise of frame t is independent of everything before it, so the estimate holds
+ * for the recursion's frame t with the previous outputs held fixed; it costs one more FLT1 and FLT2, on a perturbed
+ * frame. Under vst / nlf the estimate is in the stabilised domain, at the run's sigma. */
+#define SEQ_SURE_EPS_REL 0.05f /* the probe, in units of sigma: the middle of the plateau 0.025 .. 0.1 of DESIGN.md §9's table */
+#define SEQ_SURE_BLOCK 16      /* the tile of nlk_dev_sure_terms */
+#define SEQ_SURE_FRAME_STEP 0xD1B54A32D192ED03ull /* the seed of frame t = seed + t * this (mod 2^64) */
+struct seq_sure {
+  float eps_rel;  /* eps = eps_rel * sigma */
+  uint64_t seed;
+  int block;
+  float *d_probe, *d_flt1, *d_flt2; /* of the frame's size: the perturbed frame and its two estimates */
+  double *d_blocks;                 /* NULL, or the map of flt2's terms, [nby][nbx][ch][2] (nlk_dev_sure_terms) */
+};
+/* eps_rel, seed, block = the defaults above, seed 0; NLK_SURE_EPS (> 0) and NLK_SURE_SEED (strtoull, any base) override;
+ * one device allocation per image, with_map: also the map. Returns the first failing call's code (what was allocated
+ * stays for seq_sure_free). */
+int seq_sure_alloc(nlk_ctx *ctx, struct seq_sure *u, int w, int h, int ch, int with_map);
+void seq_sure_free(nlk_ctx *ctx, struct seq_sure *u);
+/* after seq_forward_step(s) of frame t (t = 0: the first), while work->d_noisy, d_flow and d_occ still hold that step's
+ * values: the probe on d_noisy, the two warps again when there is a previous frame, FLT1', then FLT2' with FLT1' as its
+ * basic estimate, and the terms of flt1 into d_slot[0 .. 2 ch), those of flt2 into d_slot[2 ch .. 4 ch) (device doubles,
+ * R_c and D_c interleaved). Writes u's images and work->d_warp, nothing else: s->flt1, s->flt2 and what a following
+ * seq_lag1_step reads stay as they are. Asynchronous on the context's stream; returns the first failing call's code. */
+int seq_sure_step(const struct seq_step *s, const struct seq_sure *u, long t, double *d_slot);
+/* the estimate of one pass of one frame from its 2 ch downloaded terms, added over the channels */
+struct seq_sure_est { double mse, psnr, resid, div; }; /* MSE_hat, 10 log10(255^2 / MSE_hat), R / N, D / (eps N) */
+struct seq_sure_est seq_sure_estimate(const double *terms, int w, int h, int ch, float sigma, float eps_rel);
+
 /* ---- one smoother step: frame i is smoothed against a later frame's estimate. The lag-1 smoother
  * (scripts/nlkalman-lsmo-seq.sh:87-108) does it as soon as frame i + 1 is filtered, next = flt2_{i+1}; the backward pass
  * of the whole sequence (scripts/nlkalman-seq.sh:117-150) from the last frame down, next = smo1_{i+1}. The flow

@@ -60,13 +60,22 @@ class SequenceFilter:
     second triple of OPM (default: the first). finish() gives the last frame's lsm1, its flt2.
     of="tvl1" | "bm": the flow estimator of the run, as the tools' --of. "bm": Context.bm_flow (block matching,
     DESIGN.md §9) wherever a flow is computed - push(), smooth(), lag1="tvl1"'s own flow - at of_fscale / lag1_of_fscale;
-    of_lambda is ignored and flow_iterations / lag1_flow_iterations stay empty."""
+    of_lambda is ignored and flow_iterations / lag1_flow_iterations stay empty.
+    sure=True | eps_rel: the error of every pushed frame's flt1 and flt2 is estimated without clean frames by
+    Monte-Carlo SURE (seq_sure_step of host/seq_step.c), at the cost of one more FLT1 and FLT2 on the
+    frame plus a probe of +-eps, eps = eps_rel * sigma (True: SURE_EPS_REL, or NLK_SURE_EPS). After push(), which then
+    waits for the device, .sure[-1] is a dict: mse, psnr (at 255), resid = R / N, div = D / (eps N) of flt2 over all
+    samples, mse_ch ... div_ch the same per channel (arrays), "flt1" the same dict for flt1, eps and seed as used; and
+    .sure_blocks the risk map of flt2, [nby][nbx][ch][2] = (R, D) per sure_block x sure_block tile. sure_seed (default
+    0, or NLK_SURE_SEED): frame t uses sure_seed + t * SURE_FRAME_STEP. The estimate is in the domain the filter works
+    in: under sigma="vst" | "nlf" the stabilised one, at .sigma. The smoother's outputs are not estimated."""
 
     LAG1_INVERT_STEPS = 4   # SEQ_LAG1_INVERT_STEPS of host/seq_step.h
+    SURE_EPS_REL, SURE_BLOCK, SURE_FRAME_STEP = 0.05, 16, 0xD1B54A32D192ED03   # SEQ_SURE_* of host/seq_step.h
 
     def __init__(self, ctx, w, h, ch, sigma, f1=None, f2=None, s1=None, of_lambda=0.25, of_fscale=1,
                  occ_th=0.75, keep_history=True, lag1=None, lag1_of_lambda=None, lag1_of_fscale=None,
-                 lag1_occ_th=None, of="tvl1"):
+                 lag1_occ_th=None, of="tvl1", sure=None, sure_seed=None, sure_block=None):
         pkg = _p()
         if of not in ("tvl1", "bm"):
             raise ValueError(f"SequenceFilter(of={of!r}): want 'tvl1' or 'bm'")
@@ -105,6 +114,22 @@ class SequenceFilter:
             self.occ_th2 = float(occ_th if lag1_occ_th is None else lag1_occ_th)
             self.d_fflow, self.d_focc = a(w * h * 8), a(w * h * 4)
             self.lag1_flow_iterations = []
+        self.sure_eps_rel = None
+        if sure is not None and sure is not False:
+            import os
+            env_eps, env_seed = os.environ.get("NLK_SURE_EPS"), os.environ.get("NLK_SURE_SEED")
+            if sure is True:
+                sure = float(env_eps) if env_eps and float(env_eps) > 0 else self.SURE_EPS_REL
+            if not float(sure) > 0:
+                raise ValueError(f"SequenceFilter(sure={sure!r}): want True or eps / sigma > 0")
+            self.sure_eps_rel = float(sure)
+            self.sure_seed = int(sure_seed) if sure_seed is not None else int(env_seed, 0) if env_seed else 0
+            self.sure_block = int(sure_block or self.SURE_BLOCK)
+            self.sure, self.sure_blocks = [], None
+            self._sure_img = [a(self.nbytes) for _ in range(3)]   # the perturbed frame and its two estimates
+            nby, nbx = -(-h // self.sure_block), -(-w // self.sure_block)
+            self._sure_map_shape = (nby, nbx, ch, 2)
+            self._d_sure = a(8 * (4 * ch + 2 * ch * nby * nbx))   # the terms of flt1 and flt2, then flt2's map
         self.stage_s = None   # set to {} to have push() synchronise after each stage and add up its wall times (bench.py S1)
 
     def _resolve(self, sigma):
@@ -183,6 +208,8 @@ class SequenceFilter:
             c.warp_bicubic(self.d_warp, self.flt2, self.d_flow, self.d_occ, w, h, ch)
             c.filter_frame(n2, self.d_noisy, self.d_warp, n1, w, h, ch, sg, self.f2)
             mark("warp_flt2")
+        if self.sure_eps_rel is not None:
+            self._sure_step(n1, n2)
         if self.lag1 and self.t > 0:
             self._lag1_step(n2)
         if self.flt1:
@@ -193,6 +220,41 @@ class SequenceFilter:
         if self.history is not None:
             self.history.append(n2)
         self.t += 1
+
+    def _sure_step(self, n1, n2):
+        """the estimates of this frame's flt1 (n1) and flt2 (n2) while d_noisy, d_flow and d_occ hold its values:
+        seq_sure_step of host/seq_step.c; waits for the device"""
+        c, w, h, ch, sg = self.ctx, self.w, self.h, self.ch, self.sigma
+        d_probe, q1, q2 = self._sure_img
+        eps = float(np.float32(self.sure_eps_rel) * np.float32(sg))
+        seed = (self.sure_seed + self.t * self.SURE_FRAME_STEP) & 0xFFFFFFFFFFFFFFFF
+        c.probe_add(d_probe, self.d_noisy, w * h * ch, eps, seed)
+        prev = self.t > 0
+        if prev:
+            c.warp_bicubic(self.d_warp, self.flt1, self.d_flow, self.d_occ, w, h, ch)
+        c.filter_frame(q1, d_probe, self.d_warp if prev else None, None, w, h, ch, sg, self.f1)
+        if prev:
+            c.warp_bicubic(self.d_warp, self.flt2, self.d_flow, self.d_occ, w, h, ch)
+        c.filter_frame(q2, d_probe, self.d_warp if prev else None, q1, w, h, ch, sg, self.f2)
+        d_tot, d_map = self._d_sure, self._d_sure + 8 * 4 * ch
+        c.sure_terms_dev(d_tot, None, self.d_noisy, n1, q1, w, h, ch, self.sure_block, seed)
+        c.sure_terms_dev(d_tot + 8 * 2 * ch, d_map, self.d_noisy, n2, q2, w, h, ch, self.sure_block, seed)
+        tot = c.download(d_tot, (2, ch, 2), np.float64)
+        self.sure_blocks = c.download(d_map, self._sure_map_shape, np.float64)
+        pkg = _p()
+
+        def est(t2):
+            out = {}
+            for key, R, D, n in (("", t2[:, 0].sum(), t2[:, 1].sum(), w * h * ch), ("_ch", t2[:, 0], t2[:, 1], w * h)):
+                m = R / n - sg * sg + 2.0 * sg * sg * D / (eps * n)
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    out.update({"mse" + key: m, "psnr" + key: 10.0 * np.log10(255.0 ** 2 / m), "resid" + key: R / n,
+                                "div" + key: D / (eps * n)})
+            out["mse"] = pkg.sure_mse(t2[:, 0].sum(), t2[:, 1].sum(), w * h * ch, sg, eps)
+            return out
+        rec = est(tot[1])
+        rec.update(flt1=est(tot[0]), eps=eps, seed=seed)
+        self.sure.append(rec)
 
     def _lag1_step(self, d_cur):
         """lsm1 of the previous frame from its flt2 (self.flt2), this frame's flt2 and, for "inv", this frame's

@@ -41,6 +41,8 @@
  *   nlk_nlf_build, nlk_dev_nlf_forward / _inverse
  *                                       nothing, likewise
  *   nlk_dev_ssim                        nothing: the reference measures the squared error only
+ *   nlk_dev_probe_add, nlk_dev_sure_terms, nlk_sure_mse
+ *                                       nothing: the reference measures against clean frames only
  *   nlk_dev_yuv_to_rgb / nlk_dev_rgb_to_yuv, nlk_yuv_format_from_tag, nlk_yuv_frame_bytes
  *                                       nothing: the reference reads and writes RGB image files only
  */
@@ -264,6 +266,36 @@ int nlk_dev_sqdiff_sum(nlk_ctx *ctx, double *sum, const float *a, const float *b
  * a NULL pointer other than d_map; the context keeps working after a refused call. */
 int nlk_dev_ssim(nlk_ctx *ctx, double *d_ssim, float *d_map, const float *d_a, const float *d_b, int w, int h, int ch,
                  float range);
+
+/* ---- error estimate without clean frames (restated in numpy by tests/sure_ref.py): Stein's unbiased
+ * risk estimate with the divergence taken by one Monte-Carlo probe (Ramani, Blu, Unser 2008). For a frame y of N
+ * samples under white Gaussian noise of deviation sigma, f = the filter's output and b a vector of independent signs,
+ *     MSE_hat = R / N - sigma^2 + 2 sigma^2 D / (eps N),  R = sum (y_i - f_i)^2,  D = sum b_i (f(y + eps b)_i - f(y)_i)
+ *   Sign       of sample i under a 64-bit seed, all arithmetic mod 2^64:
+ *                z = seed + (i + 1) 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;
+ *                z = (z ^ z >> 27) 0x94D049BB133111EB;   z ^= z >> 31;   b_i = -1 if bit 63 of z is set, else +1
+ *              It is recomputed wherever it is needed and never stored.
+ * nlk_dev_probe_add: out[i] = in[i] + (b_i > 0 ? eps : -eps) for i < n, one float add (a float32 numpy restatement
+ *   gives the same bits). out may be in; n = 0 is allowed; eps must be finite.
+ * nlk_dev_sure_terms: the two sums of the HWC images y (noisy), f = filter(y), fp = filter(y + eps b), every channel
+ *   by itself, i = (y w + x) ch + c:  R_c = sum ((double)y - (double)f)^2,  D_c = sum b_i ((double)fp - (double)f).
+ *   d_total[2 c] = R_c, d_total[2 c + 1] = D_c (2 ch device doubles; several calls may write to consecutive slots of
+ *   one buffer that is downloaded once). d_blocks may be NULL; otherwise it is [nby][nbx][ch][2] device doubles, nbx =
+ *   ceil(w / block), nby = ceil(h / block), and receives the same two sums over every block x block tile (ragged at
+ *   the right and bottom): the risk map. 4 <= block <= 64 (it also sets the order of summation when there is no map),
+ *   1 <= ch <= 16, w, h >= 1. Sums are in double in an order that depends on (w, h, ch, block) alone, without atomics:
+ *   the same input gives the same bits on every call; the totals are the tiles' sums added in a fixed order by a
+ *   second launch. Non-finite samples are not special-cased: one makes the terms it enters non-finite - those of its
+ *   own tile and channel (y: R; fp: D; f: both) and that channel's totals - and nothing else.
+ *   Asynchronous on the context's stream; the scratch (used when d_blocks is NULL) is kept in the context and grows
+ *   on demand.
+ * Both: NLK_EINVAL for an argument outside what is stated or a NULL pointer other than d_blocks; the context keeps
+ *   working after a refused call.
+ * nlk_sure_mse: the formula on the host, from sums over n samples (of one channel, or added over the channels). */
+int nlk_dev_probe_add(nlk_ctx *ctx, float *out, const float *in, size_t n, float eps, uint64_t seed);
+int nlk_dev_sure_terms(nlk_ctx *ctx, double *d_total, double *d_blocks, const float *d_y, const float *d_f,
+                       const float *d_fp, int w, int h, int ch, int block, uint64_t seed);
+double nlk_sure_mse(double R, double D, double n, double sigma, double eps);
 
 /* ---- noise level of an image (restated in numpy by tests/sigma_ref.py): a block-DCT percentile
  * estimator. HWC image on the 0..255 scale, w, h >= 8, ch >= 1; every channel by itself:
