@@ -6,7 +6,7 @@
 #include "nlk_internal.h"
 
 template <int PSZ>
-static int nlk_groupp_launch_t(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur,
+static int nlk_groupp_launch_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float* img, const float* cur,
                                const float* prev, float* acc, const uint8_t* active) {
   typedef NlkPP<PSZ> K;
   // Deterministic mode runs a temporal frame's far-reaching (spatial-branch) groups in a second
@@ -56,7 +56,7 @@ static int nlk_groupp_launch_t(nlk_ctx* c, const NlkGeom& g, const float* img, c
         // (flags of both passes, then their tile-row counters: 2 x (1 + nty) ints, cleared per call)
         const size_t cnt_off = (2 * ntiles + 15) & ~(size_t)15, cnt_bytes = sizeof(int) * 2 * (1 + (size_t)g.ngy);
         if ((rc = reserve(c, c->slab, sizeof(float) * need)) || (rc = reserve(c, c->tflag, cnt_off + cnt_bytes))) return rc;
-        HIPCHK(c, hipMemsetAsync((uint8_t*)c->tflag.p + cnt_off, 0, cnt_bytes, c->rv.stream));
+        HIPCHK(c, hipMemsetAsync((uint8_t*)c->tflag.p + cnt_off, 0, cnt_bytes, v.stream));
         cnt_base = (int*)((uint8_t*)c->tflag.p + cnt_off);
       }
       tl.slab = (float*)c->slab.p + slab_off;
@@ -67,11 +67,11 @@ static int nlk_groupp_launch_t(nlk_ctx* c, const NlkGeom& g, const float* img, c
     auto kern = g.smoother ? k_groupp<PSZ, true> : k_groupp<PSZ, false>;
     HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const float* basis = (const float*)c->tabs.p;
-    hipLaunchKernelGGL(kern, dim3(nlk_xcd_grid(g.ngx * g.ngy)), dim3(64), lds, c->rv.stream, img, cur, prev, g, tl,
-                       (const uint32_t*)c->rv.topk, (const NlkTarget*)c->rv.tinfo, (const uint32_t*)c->rv.gcoords,
+    hipLaunchKernelGGL(kern, dim3(nlk_xcd_grid(g.ngx * g.ngy)), dim3(64), lds, v.stream, img, cur, prev, g, tl,
+                       (const uint32_t*)v.topk, (const NlkTarget*)v.tinfo, (const uint32_t*)v.gcoords,
                        active, basis, basis + PSZ * PSZ, acc);
     if (c->deterministic)
-      nlk_launch_gather(c->rv.stream, acc, tl.slab, tl.tflag, tl.tcount, g, tl, g.ch + 1);
+      nlk_launch_gather(v.stream, acc, tl.slab, tl.tflag, tl.tcount, g, tl, g.ch + 1);
     HIPCHK(c, hipGetLastError());
   }
   return NLK_OK;

@@ -70,27 +70,25 @@ int upload_tables(nlk_ctx* c, int psz) {
   return NLK_OK;
 }
 
-int launch_group(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur,
+int launch_group(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float* img, const float* cur,
                  const float* prev, float* acc, const uint8_t* active) {
   // Default: 8x8 patches with 1 or 3 channels on the matrix cores (k_group8m.h: 1.04 ms at C2 against
   // 1.34 ms for the packed-lane kernel), everything else on the packed-lane kernel (k_groupp.h; its
   // per-lane candidate lists hold up to 128 entries). Comparison variants: NLK_GROUP_PACKED=1 (8x8 on
   // k_groupp), NLK_GROUP_DPP=1 (8x8: registers + DPP), NLK_GENERIC_GROUP=1 (LDS-DCT kernel). Lists of more than 128
   // entries (capacity k or group size) go to the LDS-DCT kernel (k_group_lds.h): its fixed shapes where they are
-  // instantiated - patch sizes 4 / 6 / 8 / 10 / 12 / 16 with 1 or 3 channels - and its run-time shape (patch size and
-  // channel count from NlkGeom) otherwise, as patches above 16 do
-  const bool ch13 = g.ch == 1 || g.ch == 3;
+  // instantiated (nlk_fixed_shape) and its run-time shape (patch size and channel count from NlkGeom) otherwise, as
+  // patches above 16 do
   const bool lists_fit = g.kmax <= 128 && g.gstride <= 128;
-  const bool lds_dct = ch13 && (g.psz == 4 || g.psz == 6 || g.psz == 8 || g.psz == 10 || g.psz == 12 || g.psz == 16);
-  if (g.psz > 16) return nlk_launch_group_any(c, g, img, cur, prev, acc, active);  // (GroupAny: 17..32)
+  if (g.psz > 16) return nlk_launch_group_any(c, v, g, img, cur, prev, acc, active);  // (GroupAny: 17..32)
   if (nlk_set(c->sw.generic_group) || !lists_fit)
-    return lds_dct ? nlk_launch_group_generic(c, g, img, cur, prev, acc, active)
-                   : nlk_launch_group_any(c, g, img, cur, prev, acc, active);
-  if (g.psz == 8 && ch13 && !nlk_set(c->sw.group_packed))
-    return nlk_launch_group8(c, g, img, cur, prev, acc, active);
-  if (g.psz <= 8) return nlk_launch_groupp_a(c, g, img, cur, prev, acc, active);
-  if (g.psz <= 12) return nlk_launch_groupp_b(c, g, img, cur, prev, acc, active);
-  return nlk_launch_groupp_c(c, g, img, cur, prev, acc, active);
+    return nlk_fixed_shape(g.psz, g.ch) ? nlk_launch_group_generic(c, v, g, img, cur, prev, acc, active)
+                                        : nlk_launch_group_any(c, v, g, img, cur, prev, acc, active);
+  if (g.psz == 8 && nlk_fixed_shape(g.psz, g.ch) && !nlk_set(c->sw.group_packed))
+    return nlk_launch_group8(c, v, g, img, cur, prev, acc, active);
+  if (g.psz <= 8) return nlk_launch_groupp_a(c, v, g, img, cur, prev, acc, active);
+  if (g.psz <= 12) return nlk_launch_groupp_b(c, v, g, img, cur, prev, acc, active);
+  return nlk_launch_groupp_c(c, v, g, img, cur, prev, acc, active);
 }
 
 int check_images(nlk_ctx* c, const void* out, const void* cur, int w, int h, int ch) {
@@ -99,6 +97,12 @@ int check_images(nlk_ctx* c, const void* out, const void* cur, int w, int h, int
   if (w <= 0 || h <= 0 || ch <= 0) return fail(c, NLK_EINVAL, "bad image size %dx%dx%d", w, h, ch);
   if (w > 65535 || h > 65535) return fail(c, NLK_EUNSUP, "image side above 65535");
   return NLK_OK;
+}
+
+// the opening check of a frame call: its images and its parameters
+int check_frame(nlk_ctx* c, const void* out, const void* cur, int w, int h, int ch, const struct nlkalman_params* P) {
+  const int rc = check_images(c, out, cur, w, h, ch);
+  return rc ? rc : (P ? NLK_OK : fail(c, NLK_EINVAL, "null parameters"));
 }
 
 // event i of the current frame call; event 0 opens a new set
@@ -404,15 +408,17 @@ struct NlkPlan {
   bool generic = false;          // k_bm_generic instead of the tiled kernels
 };
 
-// records of the target rows from `r0` on (a view into the call's buffers)
-static NlkRecView view_rows(nlk_ctx* c, const NlkGeom& g, hipStream_t stream, int r0, int band) {
+// records of the target rows from `r0` on (a view into the call's buffers; `marks_ext`: the mark words go to the
+// caller's array instead of the context's)
+static NlkRecView view_rows(nlk_ctx* c, const NlkGeom& g, hipStream_t stream, int r0, int band,
+                            uint64_t* marks_ext = nullptr) {
   const size_t t0 = (size_t)r0 * g.ngx;
   NlkRecView v;
   v.stream = stream;
   v.topk = (uint32_t*)c->topk.p + t0 * g.kmax;
   v.tinfo = (NlkTarget*)c->tinfo.p + t0;
   v.gcoords = (uint32_t*)c->gcoords.p + t0 * g.gstride;
-  v.marks = (c->marks_ext ? c->marks_ext : (uint64_t*)c->marks.p) + t0;
+  v.marks = (marks_ext ? marks_ext : (uint64_t*)c->marks.p) + t0;
   v.wide = (uint32_t*)c->wide.p + t0 + band;  // (every band: its own counter in front of its own list)
   return v;
 }
@@ -426,23 +432,25 @@ static NlkGeom band_geom(const NlkGeom& g, int r0, int rows) {
 }
 
 // layout of the pixel rows [y0, y1) (planar copies, row test of the validity map, accumulator rows cleared) and
-// the validity map's column test for the rows [v0, v1) (a row needs the row tests of the psz rows from it on)
-static int layout_rows(nlk_ctx* c, const float* cur, const float* prev, const float* basic, float* acc_zero, int w,
-                       int h, int ch, int psz, int y0, int y1, int v0, int v1, uint32_t* zero_word = nullptr) {
+// the validity map's column test for the rows [v0, v1) (a row needs the row tests of the psz rows from it on), on
+// `stream`. `diff`: where a smoother call keeps planar prev - cur (NlkPlan::img_diff), else nullptr
+static int layout_rows(nlk_ctx* c, hipStream_t stream, const float* cur, const float* prev, const float* basic,
+                       float* acc_zero, const float* diff, int w, int h, int ch, int psz, int y0, int y1, int v0, int v1,
+                       uint32_t* zero_word = nullptr) {
   // (every image is copied into the context's slab, one channel too: the group kernel addresses all of them from
   // one base pointer)
   const size_t img_floats = (size_t)w * h * ch;
   float* const slab = (float*)c->planes.p;
   if (y1 > y0)
-    hipLaunchKernelGGL(ch == 3 ? k_layout<3> : k_layout<0>, dim3((w + 255) / 256, y1 - y0), dim3(256), 0, c->stream, cur, slab, prev,
+    hipLaunchKernelGGL(ch == 3 ? k_layout<3> : k_layout<0>, dim3((w + 255) / 256, y1 - y0), dim3(256), 0, stream, cur, slab, prev,
                        slab + img_floats, basic, slab + 2 * img_floats, (uint8_t*)c->rowok.p, acc_zero, w, h, ch, psz,
-                       1, y0, zero_word, (c->layout_diff && prev) ? slab + 3 * img_floats : nullptr);
+                       1, y0, zero_word, const_cast<float*>(diff));
   if (prev && v1 > v0) {
     if (w % 4 == 0)
-      hipLaunchKernelGGL(k_nan_cols4, dim3((w / 4 + 255) / 256, v1 - v0), dim3(256), 0, c->stream,
+      hipLaunchKernelGGL(k_nan_cols4, dim3((w / 4 + 255) / 256, v1 - v0), dim3(256), 0, stream,
                          (const uint32_t*)c->rowok.p, (uint32_t*)c->vmap.p, w / 4, h, psz, v0);
     else
-      hipLaunchKernelGGL(k_nan_cols, dim3((w + 255) / 256, v1 - v0), dim3(256), 0, c->stream, (const uint8_t*)c->rowok.p,
+      hipLaunchKernelGGL(k_nan_cols, dim3((w + 255) / 256, v1 - v0), dim3(256), 0, stream, (const uint8_t*)c->rowok.p,
                          (uint8_t*)c->vmap.p, w, h, psz, v0);
   }
   HIPCHK(c, hipGetLastError());
@@ -453,12 +461,10 @@ static int layout_rows(nlk_ctx* c, const float* cur, const float* prev, const fl
 static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* prev, const float* basic, int w,
                       int h, int ch, float sigma, const struct nlkalman_params* P, int oy, int ngy,
                       int smoother, int nbands, float* acc_zero = nullptr, bool do_layout = true) {
-  int rc = check_images(c, cur, cur, w, h, ch);
+  int rc = check_frame(c, cur, cur, w, h, ch, P);
   if (rc) return rc;
-  if (!P) return fail(c, NLK_EINVAL, "null parameters");
   NLK_USE_DEVICE(c);
-  c->lazy_ngx = c->lazy_ngy = 0;  // (whatever replays this call's mask: `active` holds its bytes unless set again)
-  c->lazy_dst = nullptr;
+  nlk_set_lazy_active(c, 0, 0, nullptr);  // (whatever replays this call's mask: `active` holds its bytes unless set again)
   NlkGeom& g = pl.g;
   g.w = w; g.h = h; g.ch = ch;
   g.psz = P->patch_sz;
@@ -492,8 +498,7 @@ static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* pr
   const int ncand = (2 * wmax + 1) * (2 * wmax + 1);
   // the tiled matching kernels exist for patch sizes 4 / 6 / 8 / 10 / 12 / 16, 1 or 3 channels and
   // windows of up to 1024 candidates; everything else the reference accepts goes to k_bm_generic
-  pl.generic = !(g.psz == 4 || g.psz == 6 || g.psz == 8 || g.psz == 10 || g.psz == 12 || g.psz == 16) ||
-               !(ch == 1 || ch == 3) || ncand > 64 * 16 || nlk_set(c->sw.generic_match);
+  pl.generic = !nlk_fixed_shape(g.psz, ch) || ncand > 64 * 16 || nlk_set(c->sw.generic_match);
   g.kmax = max(max(g.npx, g.npt), 1);
   const int ngrid = g.ngx * g.ngy;
   const int npix = w * h;
@@ -507,10 +512,9 @@ static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* pr
     // planar copies of the (up to) three images in ONE allocation: [cur | prev | basic]
     const size_t img_floats = (size_t)npix * ch;
     // (a smoother call keeps a fourth image, prev - cur: what the pass B of k_group8m<.., true, ..> transforms)
-    c->layout_diff = g.smoother && prev != nullptr;
-    if ((rc = reserve(c, c->planes, sizeof(float) * img_floats * (c->layout_diff ? 4 : (basic ? 3 : (prev ? 2 : 1)))))) return rc;
-    pl.img_diff = c->layout_diff ? (const float*)c->planes.p + 3 * img_floats : nullptr;
-    c->p_diff = pl.img_diff;
+    const bool keep_diff = g.smoother && prev != nullptr;
+    if ((rc = reserve(c, c->planes, sizeof(float) * img_floats * (keep_diff ? 4 : (basic ? 3 : (prev ? 2 : 1)))))) return rc;
+    pl.img_diff = keep_diff ? (const float*)c->planes.p + 3 * img_floats : nullptr;
     pl.img_cur = (const float*)c->planes.p;
     pl.img_prev = prev ? pl.img_cur + img_floats : nullptr;
     pl.img_basic = basic ? pl.img_cur + 2 * img_floats : nullptr;
@@ -518,8 +522,9 @@ static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* pr
     if ((rc = reserve(c, c->wide, sizeof(uint32_t) * ((size_t)ngrid + nbands)))) return rc;  // per band: queue length + queue
     if (do_layout) {
       // (the layout kernel also clears the length of the first band's wide-window queue: one 6 us memset less)
-      int rc2 = layout_rows(c, cur, prev, basic, acc_zero, w, h, ch, g.psz, 0, h, 0, h, (uint32_t*)c->wide.p);
-      if (rc2) return rc2;
+      if ((rc = layout_rows(c, c->stream, cur, prev, basic, acc_zero, pl.img_diff, w, h, ch, g.psz, 0, h, 0, h,
+                            (uint32_t*)c->wide.p)))
+        return rc;
       pl.wide0_zeroed = true;
     }
   }
@@ -612,30 +617,48 @@ static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* pr
     if (pl.lds_w > 160 * 1024) { pl.generic = true; pl.wide = false; }
     pl.maxm_w = (ncand + 63) / 64;
   }
-  c->p_match = pl.img_match; c->p_cur = pl.img_cur; c->p_prev = pl.img_prev;
-  c->last = g;
-  c->have_last = true;
+  c->last = {g, pl.img_match, pl.img_cur, pl.img_prev, pl.img_diff, true};
   return NLK_OK;
 }
 
 // phase 1 for the target rows [r0, r0 + rows) of the plan: block matching + selection on `stream`;
-// leaves topk / gcoords / tinfo / marks of those rows in the context's buffers
-static int match_rows(nlk_ctx* c, const NlkPlan& pl, hipStream_t stream, int r0, int rows, int band) {
+// leaves topk / gcoords / tinfo of those rows in the context's buffers, and their mark words there or in `marks_ext`
+static int match_rows(nlk_ctx* c, const NlkPlan& pl, hipStream_t stream, int r0, int rows, int band,
+                      uint64_t* marks_ext = nullptr) {
   const NlkGeom gb = band_geom(pl.g, r0, rows);
-  c->rv = view_rows(c, pl.g, stream, r0, band);
-  if (pl.generic) return nlk_launch_match_generic(c, gb, pl.img_match);
+  const NlkRecView v = view_rows(c, pl.g, stream, r0, band, marks_ext);
+  if (pl.generic) return nlk_launch_match_generic(c, v, gb, pl.img_match);
   NlkTile tl = pl.tl;
   tl.nty = (rows + tl.tgy - 1) / tl.tgy;
   if (pl.wide && !(pl.wide0_zeroed && r0 == 0 && band == 0))
-    HIPCHK(c, hipMemsetAsync(c->rv.wide, 0, sizeof(uint32_t), stream));
-  int rc = nlk_launch_match(c, gb, tl, pl.lds, pl.img_match, pl.maxm, false);
+    HIPCHK(c, hipMemsetAsync(v.wide, 0, sizeof(uint32_t), stream));
+  int rc = nlk_launch_match(c, v, gb, tl, pl.lds, pl.img_match, pl.maxm, false);
   if (rc) return rc;
   if (pl.wide) {
     NlkTile tw = pl.tw;
     tw.nty = tl.nty;
-    rc = nlk_launch_match(c, gb, tw, pl.lds_w, pl.img_match, pl.maxm_w, true);
+    rc = nlk_launch_match(c, v, gb, tw, pl.lds_w, pl.img_match, pl.maxm_w, true);
   }
   return rc;
+}
+
+// The bit-plane scratch of the row replay (k_commit_rows.h assumes exactly this): planes per grid row, rows per
+// batch, and the rows the arrays hold - whole batches (a band's last batch may run into the rows of the next) + 3
+struct NlkPlaneLayout {
+  int np, batch, rows_pad;
+};
+static NlkPlaneLayout plane_layout(int R, int rows) {
+  const int np = R + R * (2 * R + 1);  // (reach 1: 4)
+  const int batch = R == 1 ? NLK_CR_BATCH : 48 / np;
+  return {np, batch, (rows + batch - 1) / batch * batch + 3 * batch};
+}
+
+// the bit planes of the grid rows [first, first + nrows) from their mark words (reach 1..3); `gen`: the in-launch
+// replay's generation counter, advanced by the kernel (else nullptr)
+static void launch_marks_planes(hipStream_t stream, int R, const uint64_t* marks, uint32_t* planes, int ngx, int first,
+                                int nrows, uint32_t* gen) {
+  auto kern = R == 1 ? k_marks_planes1 : (R == 2 ? k_marks_planes<2> : k_marks_planes<3>);
+  hipLaunchKernelGGL(kern, dim3(8, nrows), dim3(256), 0, stream, marks, planes, ngx, first, gen);
 }
 
 // phase 2: replay of the raster-order processed mask over the mark words of the grid rows
@@ -650,41 +673,18 @@ static int commit_rows(nlk_ctx* c, hipStream_t stream, const uint64_t* marks, ui
     HIPCHK(c, hipMemsetAsync(active + (size_t)first * ngx, 1, (size_t)nrows * ngx, stream));
     return NLK_OK;
   }
-  if (R == 1 && ngx <= 2048 && !nlk_set(c->sw.commit_wave) && !nlk_set(c->sw.commit_lds) && !nlk_set(c->sw.commit_band)) {
-    // reach 1: one grid row per step on bit planes (k_commit.h); the arrays cover the whole grid, padded to
-    // whole batches (a band's last batch may run into the rows of the next): 4 planes + decisions + row states
-    const int rows_pad = (total + NLK_CR_BATCH - 1) / NLK_CR_BATCH * NLK_CR_BATCH + 3 * NLK_CR_BATCH;
-    int rc = reserve(c, c->skew, sizeof(uint32_t) * (size_t)rows_pad * 6 * 64);
-    if (rc) return rc;
-    uint32_t* planes = (uint32_t*)c->skew.p;
-    uint32_t* actbits = planes + (size_t)rows_pad * 4 * 64;
-    uint32_t* astate = actbits + (size_t)rows_pad * 64;
-    hipLaunchKernelGGL(k_marks_planes1, dim3(8, nrows), dim3(256), 0, stream, marks, planes, ngx, first, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(k_mask_commit_rows1, dim3(1), dim3(64), 0, stream, (const uint32_t*)planes, actbits, astate, ngx,
-                       first, nrows);
-    hipLaunchKernelGGL(k_active_bytes, dim3((ngx + 255) / 256, nrows), dim3(256), 0, stream, (const uint32_t*)actbits,
-                       active, ngx, first);
-    HIPCHK(c, hipGetLastError());
-    return NLK_OK;
-  }
   if (R <= 3 && ngx <= 2048 && !nlk_set(c->sw.commit_wave) && !nlk_set(c->sw.commit_lds) && !nlk_set(c->sw.commit_band)) {
-    // reach 2 / 3: the row formulation with the in-row chain solved by iteration (k_commit.h)
-    const int np = R + R * (2 * R + 1), pf = 48 / np;
-    const int rows_pad = (total + pf - 1) / pf * pf + 3 * pf;
-    int rc = reserve(c, c->skew, sizeof(uint32_t) * (size_t)rows_pad * (np + 1 + R) * 64);
+    // one grid row per step on bit planes (k_commit.h; reach 2 / 3: the in-row chain solved by iteration); the
+    // arrays cover the whole grid: the planes, then per row the decisions (64 words) and the row states (R x 64)
+    const NlkPlaneLayout L = plane_layout(R, total);
+    int rc = reserve(c, c->skew, sizeof(uint32_t) * (size_t)L.rows_pad * (L.np + 1 + R) * 64);
     if (rc) return rc;
     uint32_t* planes = (uint32_t*)c->skew.p;
-    uint32_t* actbits = planes + (size_t)rows_pad * np * 64;
-    uint32_t* astate = actbits + (size_t)rows_pad * 64;
-    if (R == 2) {
-      hipLaunchKernelGGL(k_marks_planes<2>, dim3(8, nrows), dim3(256), 0, stream, marks, planes, ngx, first, (uint32_t*)nullptr);
-      hipLaunchKernelGGL(k_mask_commit_rows<2>, dim3(1), dim3(64), 0, stream, (const uint32_t*)planes, actbits, astate,
-                         ngx, first, nrows);
-    } else {
-      hipLaunchKernelGGL(k_marks_planes<3>, dim3(8, nrows), dim3(256), 0, stream, marks, planes, ngx, first, (uint32_t*)nullptr);
-      hipLaunchKernelGGL(k_mask_commit_rows<3>, dim3(1), dim3(64), 0, stream, (const uint32_t*)planes, actbits, astate,
-                         ngx, first, nrows);
-    }
+    uint32_t* actbits = planes + (size_t)L.rows_pad * L.np * 64;
+    uint32_t* astate = actbits + (size_t)L.rows_pad * 64;
+    launch_marks_planes(stream, R, marks, planes, ngx, first, nrows, nullptr);
+    hipLaunchKernelGGL(R == 1 ? k_mask_commit_rows1 : (R == 2 ? k_mask_commit_rows<2> : k_mask_commit_rows<3>), dim3(1),
+                       dim3(64), 0, stream, (const uint32_t*)planes, actbits, astate, ngx, first, nrows);
     hipLaunchKernelGGL(k_active_bytes, dim3((ngx + 255) / 256, nrows), dim3(256), 0, stream, (const uint32_t*)actbits,
                        active, ngx, first);
     HIPCHK(c, hipGetLastError());
@@ -721,12 +721,12 @@ static int commit_rows(nlk_ctx* c, hipStream_t stream, const uint64_t* marks, ui
   if (R > 3) {
     // (2R+1)^2 neighbours do not fit the 64-bit mark words: replay from the group-coordinate lists of
     // the match phase that has just run in this context (k_mask_commit_lists)
-    if (!c->have_last || c->last.ngx != ngx || c->last.ngy != ngy || c->last.R != R ||
-        marks != (const uint64_t*)c->marks.p)
+    const NlkGeom& lg = c->last.g;
+    if (!c->last.valid || lg.ngx != ngx || lg.ngy != ngy || lg.R != R || marks != (const uint64_t*)c->marks.p)
       return fail(c, NLK_EUNSUP, "group reach %d grid cells > 3: the mask replay needs the coordinate lists of the "
                   "context's own match phase (row strips across GPUs are limited to reach 3)", R);
     hipLaunchKernelGGL(k_mask_commit_lists, dim3(1), dim3(1024), 0, stream, (const NlkTarget*)c->tinfo.p,
-                       (const uint32_t*)c->gcoords.p, c->last.gstride, active, ngx, ngy, R, c->last.step, c->last.oy);
+                       (const uint32_t*)c->gcoords.p, lg.gstride, active, ngx, ngy, R, lg.step, lg.oy);
     HIPCHK(c, hipGetLastError());
     return NLK_OK;
   }
@@ -759,38 +759,43 @@ static bool chase_selected(const nlk_ctx* c, const NlkGeom& g) {
 // bit planes of the grid rows [0, nrows) + a fresh generation of tagged words (the counter lives on the device and
 // is advanced by the bit-plane kernel: a step captured into a HIP graph gets a new generation at every replay)
 static int chase_prepare(nlk_ctx* c, hipStream_t stream, const uint64_t* marks, int ngx, int nrows, int R) {
-  const int np = R == 1 ? 4 : R + R * (2 * R + 1), pf = R == 1 ? NLK_CR_BATCH : 48 / np;
-  const int rows_pad = (nrows + pf - 1) / pf * pf + 3 * pf;
-  int rc = reserve(c, c->skew, sizeof(uint32_t) * (size_t)rows_pad * np * 64);
+  const NlkPlaneLayout L = plane_layout(R, nrows);
+  int rc = reserve(c, c->skew, sizeof(uint32_t) * (size_t)L.rows_pad * L.np * 64);
   if (rc) return rc;
   const size_t wbytes = sizeof(uint64_t) * (size_t)(nrows + 4 * NLK_CR_BATCH + 1) * 64;
   if (wbytes > c->chase.cap) {
     if ((rc = reserve(c, c->chase, wbytes))) return rc;
     HIPCHK(c, hipMemsetAsync(c->chase.p, 0, c->chase.cap, stream));  // (generation 0; no word of another life carries one)
   }
-  uint32_t* planes = (uint32_t*)c->skew.p;
-  uint32_t* gen = (uint32_t*)c->chase.p;
-  if (R == 1) hipLaunchKernelGGL(k_marks_planes1, dim3(8, nrows), dim3(256), 0, stream, marks, planes, ngx, 0, gen);
-  else if (R == 2) hipLaunchKernelGGL(k_marks_planes<2>, dim3(8, nrows), dim3(256), 0, stream, marks, planes, ngx, 0, gen);
-  else hipLaunchKernelGGL(k_marks_planes<3>, dim3(8, nrows), dim3(256), 0, stream, marks, planes, ngx, 0, gen);
+  launch_marks_planes(stream, R, marks, (uint32_t*)c->skew.p, ngx, 0, nrows, (uint32_t*)c->chase.p);
   HIPCHK(c, hipGetLastError());
   return NLK_OK;
 }
 
-// phase 3 for the target rows [r0, r0 + rows) of the last plan (c->last)
+// phase 3 for the target rows [r0, r0 + rows) of the last plan (c->last); `chase`: the mask replay the launch is
+// to run itself (nullptr: the decisions are in `active_rows`)
 static int group_rows(nlk_ctx* c, hipStream_t stream, float* acc, const uint8_t* active_rows, int r0, int rows,
-                      int band) {
-  const NlkGeom gb = band_geom(c->last, r0, rows);
-  c->rv = view_rows(c, c->last, stream, r0, band);
-  if (c->chase_on) {
-    c->rv.chase_planes = (const uint32_t*)c->skew.p;
-    c->rv.chase_words = (uint64_t*)c->chase.p + 64;
-    c->rv.chase_gen = (const uint32_t*)c->chase.p;
-    c->rv.chase_reach = c->last.R;
-    c->rv.chase_row0 = c->chase_row0;
-    c->rv.chase_rows = c->chase_rows;
-  }
-  return launch_group(c, gb, c->p_match, c->p_cur, c->p_prev, acc, active_rows);
+                      int band, const NlkChase* chase = nullptr) {
+  const NlkGeom gb = band_geom(c->last.g, r0, rows);
+  NlkRecView v = view_rows(c, c->last.g, stream, r0, band);
+  if (chase) v.chase = *chase;
+  return launch_group(c, v, gb, c->last.match, c->last.cur, c->last.prev, acc, active_rows);
+}
+
+// Phases 2 + 3 with the replay inside the group launch, on the context's stream: the bit planes of the grid rows
+// [0, rows) of `marks`, then the groups of the last plan's target rows, whose first is grid row `row0`. The decisions
+// stay tagged words; nlk_ctx_flush_active expands them into `lazy_dst` (nullptr: the context's own array) on demand.
+static int chase_group(nlk_ctx* c, float* acc, const uint64_t* marks, const uint8_t* active_rows, int ngx, int row0,
+                       int rows, int R, unsigned char* lazy_dst) {
+  int rc = chase_prepare(c, c->stream, marks, ngx, rows, R);
+  if (rc) return rc;
+  mark(c, 3);
+  const uint32_t* gen = (const uint32_t*)c->chase.p;  // ([0] the generation counter, from word 64 on the tagged words)
+  const NlkChase chase = {(const uint32_t*)c->skew.p, (uint64_t*)c->chase.p + 64, gen, R, row0, rows};
+  if ((rc = group_rows(c, c->stream, acc, active_rows, 0, c->last.g.ngy, 0, &chase))) return rc;
+  nlk_set_lazy_active(c, ngx, rows, lazy_dst);
+  mark(c, 4);
+  return NLK_OK;
 }
 
 // Bands of a whole-frame call (NLK_BANDS=<n>, default 1 = off). The mask replay runs on ONE compute
@@ -800,16 +805,20 @@ static int group_rows(nlk_ctx* c, hipStream_t stream, float* acc, const uint8_t*
 // 1.77 with four - the two bands' match kernels share the chip instead of finishing one after the
 // other, and the four cross-stream dependencies and the doubled launches cost what the hidden replay
 // gains. Kept as an option (and as the exactness test of banding); profiling always runs one band.
+// at most 8 bands, and none so thin that there is nothing to gain
+static int clamp_bands(int nb, int ngy, int R) {
+  nb = nb < 1 ? 1 : (nb > 8 ? 8 : nb);
+  while (nb > 1 && ngy / nb < 4 * (R + 1) + 8) --nb;
+  return nb;
+}
+
 static int frame_bands(const nlk_ctx* c, const NlkGeom& g) {
   if (c->profiling || c->deterministic || g.R == 0 || g.R > 3) return 1;  // (deterministic mode: one slab set, one sum order)
   // default: one band for reach 1 (the replay is 2 % of a frame); four for reach 2 / 3, i.e. spatial frames of
   // small patches: their replay was the diagonal one until round 4 (0.28 ms of a first frame at 1080p on one
   // compute unit); as the iterated row replay it takes 0.08 ms, and four bands still win (first frame at 1080p:
   // 2.09-2.10 ms with one band, 2.04-2.10 with two, 2.01-2.05 with four; 2.13 with the diagonal replay in four)
-  int nb = nlk_or(c->sw.bands, g.R >= 2 ? 4 : 1);
-  nb = nb < 1 ? 1 : (nb > 8 ? 8 : nb);
-  while (nb > 1 && g.ngy / nb < 4 * (g.R + 1) + 8) --nb;  // (thin bands: nothing to gain)
-  return nb;
+  return clamp_bands(nlk_or(c->sw.bands, g.R >= 2 ? 4 : 1), g.ngy, g.R);
 }
 
 // `clear`: the accumulator is cleared by the layout kernel (whole-frame calls)
@@ -827,18 +836,8 @@ static int frame_accumulate(nlk_ctx* c, float* acc, const float* cur, const floa
   if (nb == 1) {
     if ((rc = match_rows(c, pl, c->stream, 0, g.ngy, 0))) return rc;
     mark(c, 2);
-    if (chase_selected(c, g)) {
-      if ((rc = chase_prepare(c, c->stream, (const uint64_t*)c->marks.p, g.ngx, g.ngy, g.R))) return rc;
-      mark(c, 3);
-      c->chase_on = true;  // (group_rows' view of the records carries the planes / words / generation)
-      c->chase_row0 = 0; c->chase_rows = g.ngy;
-      rc = group_rows(c, c->stream, acc, active, 0, g.ngy, 0);
-      c->chase_on = false;
-      if (rc) return rc;
-      c->lazy_ngx = g.ngx; c->lazy_ngy = g.ngy;  // (the bytes of `active` only when somebody reads the records)
-      mark(c, 4);
-      return NLK_OK;
-    }
+    if (chase_selected(c, g))  // (the bytes of `active` only when somebody reads the records)
+      return chase_group(c, acc, (const uint64_t*)c->marks.p, active, g.ngx, 0, g.ngy, g.R, nullptr);
     if ((rc = commit_rows(c, c->stream, (const uint64_t*)c->marks.p, active, g.ngx, 0, g.ngy, g.R))) return rc;
     mark(c, 3);
     if ((rc = group_rows(c, c->stream, acc, active, 0, g.ngy, 0))) return rc;
@@ -895,19 +894,17 @@ int nlk_dev_strip_match_part(nlk_ctx* c, const float* cur, const float* prev, co
   int rc = plan_frame(c, pl, cur, prev, basic, w, h, ch, sigma, P, oy, ngy, smoother, 1, nullptr, false);
   if (rc) return rc;
   // (nlk_ctx_set_strip_accumulator: the rows laid out are also the accumulator rows cleared - no separate memset)
-  if ((rc = layout_rows(c, cur, prev, basic, c->strip_acc, w, h, ch, pl.g.psz, lay0, lay1, v0, v1))) return rc;
+  if ((rc = layout_rows(c, c->stream, cur, prev, basic, c->strip_acc, pl.img_diff, w, h, ch, pl.g.psz, lay0, lay1, v0, v1)))
+    return rc;
   mark(c, 1);
   if (r0 < 0 || rows < 0 || r0 + rows > pl.g.ngy) return fail(c, NLK_EINVAL, "rows [%d, %d) outside the strip's %d target rows", r0, r0 + rows, pl.g.ngy);
   if (marks_out && pl.g.R > 3)
     return fail(c, NLK_EUNSUP, "group reach %d grid cells > 3: 64-bit mark words cannot describe it (row strips "
                 "across GPUs are limited to reach 3; whole-frame calls are not)", pl.g.R);
   // the matcher writes the mark words of these rows straight to their place in the caller's array
-  c->marks_ext = (uint64_t*)marks_out;
-  rc = rows > 0 ? match_rows(c, pl, c->stream, r0, rows, 0) : NLK_OK;
-  c->marks_ext = nullptr;
-  if (rc) return rc;
+  if (rows > 0 && (rc = match_rows(c, pl, c->stream, r0, rows, 0, (uint64_t*)marks_out))) return rc;
   mark(c, 2);
-  if (reach) *reach = c->last.R;
+  if (reach) *reach = pl.g.R;
   return NLK_OK;
 }
 
@@ -941,10 +938,10 @@ int nlk_dev_mask_commit(nlk_ctx* c, const void* marks, int ngx, int ngy, int rea
 }
 
 int nlk_dev_strip_group(nlk_ctx* c, float* acc, const unsigned char* active) {
-  if (!c || !c->have_last) return fail(c, NLK_EINVAL, "nlk_dev_strip_match has not run");
+  if (!c || !c->last.valid) return fail(c, NLK_EINVAL, "nlk_dev_strip_match has not run");
   if (!acc || !active) return fail(c, NLK_EINVAL, "null accumulator / active flags");
   NLK_USE_DEVICE(c);
-  int rc = group_rows(c, c->stream, acc, active, 0, c->last.ngy, 0);
+  int rc = group_rows(c, c->stream, acc, active, 0, c->last.g.ngy, 0);
   mark(c, 4);
   return rc;
 }
@@ -955,27 +952,17 @@ int nlk_dev_strip_group(nlk_ctx* c, float* acc, const unsigned char* active) {
 // nlk_dev_strip_group on `active + gy0 * ngx`.
 int nlk_dev_strip_commit_group(nlk_ctx* c, float* acc, const void* marks, int ngx, int ngy, int reach, int gy0,
                                unsigned char* active) {
-  if (!c || !c->have_last) return fail(c, NLK_EINVAL, "nlk_dev_strip_match has not run");
-  if (!acc || !marks || !active || ngx < 1 || ngy < 1 || reach < 0 || gy0 < 0 || gy0 + c->last.ngy > ngy ||
-      ngx != c->last.ngx)
+  if (!c || !c->last.valid) return fail(c, NLK_EINVAL, "nlk_dev_strip_match has not run");
+  const NlkGeom& g = c->last.g;
+  if (!acc || !marks || !active || ngx < 1 || ngy < 1 || reach < 0 || gy0 < 0 || gy0 + g.ngy > ngy || ngx != g.ngx)
     return fail(c, NLK_EINVAL, "bad strip commit / group arguments");
   NLK_USE_DEVICE(c);
-  int rc;
-  if (reach == c->last.R && chase_selected(c, c->last)) {
-    const int rows = gy0 + c->last.ngy;
-    if ((rc = chase_prepare(c, c->stream, (const uint64_t*)marks, ngx, rows, reach))) return rc;
-    mark(c, 3);
-    c->chase_on = true;
-    c->chase_row0 = gy0; c->chase_rows = rows;
-    rc = group_rows(c, c->stream, acc, active + (size_t)gy0 * ngx, 0, c->last.ngy, 0);
-    c->chase_on = false;
-    c->lazy_ngx = ngx; c->lazy_ngy = rows; c->lazy_dst = active;  // (nlk_ctx_flush_active: rows [0, rows) of `active`)
-    mark(c, 4);
-    return rc;
-  }
-  if ((rc = commit_rows(c, c->stream, (const uint64_t*)marks, active, ngx, 0, ngy, reach))) return rc;
+  if (reach == g.R && chase_selected(c, g))  // (nlk_ctx_flush_active: rows [0, gy0 + g.ngy) of `active`)
+    return chase_group(c, acc, (const uint64_t*)marks, active + (size_t)gy0 * ngx, ngx, gy0, gy0 + g.ngy, reach, active);
+  int rc = commit_rows(c, c->stream, (const uint64_t*)marks, active, ngx, 0, ngy, reach);
+  if (rc) return rc;
   mark(c, 3);
-  rc = group_rows(c, c->stream, acc, active + (size_t)gy0 * ngx, 0, c->last.ngy, 0);
+  rc = group_rows(c, c->stream, acc, active + (size_t)gy0 * ngx, 0, g.ngy, 0);
   mark(c, 4);
   return rc;
 }
@@ -997,9 +984,8 @@ int nlk_dev_frame_normalize(nlk_ctx* c, float* out, const float* acc, const floa
 static int run_frame(nlk_ctx* c, float* out, const float* cur, const float* prev,
                      const float* basic, int w, int h, int ch, float sigma,
                      const struct nlkalman_params* P, int smoother) {
-  int rc = check_images(c, out, cur, w, h, ch);
+  int rc = check_frame(c, out, cur, w, h, ch, P);
   if (rc) return rc;
-  if (!P) return fail(c, NLK_EINVAL, "null parameters");
   if (P->patch_sz < 2) return fail(c, NLK_EUNSUP, "patch size %d not supported", P->patch_sz);
   NLK_USE_DEVICE(c);
   const size_t accb = sizeof(float) * (size_t)w * h * (ch + 1);
@@ -1040,9 +1026,8 @@ int nlk_dev_smooth_frame(nlk_ctx* c, float* smoo1, const float* filt1, const flo
 // (frame_accumulate), i.e. the whole-frame call's decisions and sums.
 static int frame_host(nlk_ctx* c, float* out_h, const float* cur_h, const float* prev_h, const float* basic_h, int w,
                       int h, int ch, float sigma, const struct nlkalman_params* P, int smoother) {
-  int rc = check_images(c, out_h, cur_h, w, h, ch);
+  int rc = check_frame(c, out_h, cur_h, w, h, ch, P);
   if (rc) return rc;
-  if (!P) return fail(c, NLK_EINVAL, "null parameters");
   NLK_USE_DEVICE(c);
   const size_t npix = (size_t)w * h, bytes = sizeof(float) * npix * ch, rowb = sizeof(float) * (size_t)w * ch;
   if ((rc = reserve(c, c->hw_cur, bytes)) || (rc = reserve(c, c->hw_out, bytes)) ||
@@ -1055,9 +1040,8 @@ static int frame_host(nlk_ctx* c, float* out_h, const float* cur_h, const float*
   const int ngy = (psz >= 2 && h >= psz) ? (h - psz) / step + 1 : 0;
   const int wall = smoother ? P->search_sz_t : max(P->search_sz_x, P->search_sz_t);  // reach of any window / group
   const int R = ((smoother || prev_h) ? P->search_sz_t : P->search_sz_x) / max(step, 1);
-  int nb = nlk_or(c->sw.host_bands, 5);  // (1080p: 2 bands 2.43 ms, 3 2.30, 4 2.25, 5 2.20, 6 2.22; one upload + call + download 2.9)
-  nb = nb < 1 ? 1 : (nb > 8 ? 8 : nb);
-  while (nb > 1 && ngy / nb < 4 * (R + 1) + 8) --nb;
+  // (1080p: 2 bands 2.43 ms, 3 2.30, 4 2.25, 5 2.20, 6 2.22; one upload + call + download 2.9)
+  const int nb = clamp_bands(nlk_or(c->sw.host_bands, 5), ngy, R);
   if (nb < 2 || R > 3 || c->deterministic || c->profiling || psz > 16 || w < psz || h < psz) {
     // small frames, masks replayed from the coordinate lists, deterministic slabs, per-kernel timing, and
     // everything the frame call rejects: one upload, the whole-frame call, one download
@@ -1094,7 +1078,6 @@ static int frame_host(nlk_ctx* c, float* out_h, const float* cur_h, const float*
   const bool trace = nlk_set(c->sw.host_trace);
   struct timespec ts0, ts1, ts2;
   if (trace) clock_gettime(CLOCK_MONOTONIC, &ts0);
-  hipStream_t const home = c->stream;
   for (int b = 0; b < nb; ++b) {
     const int r0 = (int)((long)ngy * b / nb), r1 = (int)((long)ngy * (b + 1) / nb);
     const bool last = b + 1 == nb;
@@ -1109,10 +1092,7 @@ static int frame_host(nlk_ctx* c, float* out_h, const float* cur_h, const float*
     HIPCHK(c, hipStreamWaitEvent(s, c->band_ev[E_UP][b], 0));
     if (b > 0) HIPCHK(c, hipStreamWaitEvent(s, c->band_ev[E_LAY][b - 1], 0));  // (the column test reads the rows before)
     const int v1 = last ? h : up1 - psz + 1;
-    c->stream = s;  // (the layout helpers launch on the context's stream)
-    rc = layout_rows(c, d_cur, d_prev, d_basic, acc, w, h, ch, psz, up0, up1, v0, v1);
-    c->stream = home;
-    if (rc) return rc;
+    if ((rc = layout_rows(c, s, d_cur, d_prev, d_basic, acc, pl.img_diff, w, h, ch, psz, up0, up1, v0, v1))) return rc;
     HIPCHK(c, hipEventRecord(c->band_ev[E_LAY][b], s));
     if ((rc = match_rows(c, pl, s, r0, r1 - r0, b))) return rc;
     if (b > 0) HIPCHK(c, hipStreamWaitEvent(s, c->band_ev[E_MASK][b - 1], 0));
@@ -1183,23 +1163,22 @@ int nlk_host_tables(int psz, float* basis, float* window, float* basis12_regs) {
 // context's own, read by nlk_ctx_read_records) and waits for it. No-op otherwise.
 int nlk_ctx_flush_active(nlk_ctx* c) {
   if (!c) return fail(nullptr, NLK_EINVAL, "null context");
-  if (!c->lazy_ngx) return NLK_OK;
+  if (!nlk_active_is_lazy(c)) return NLK_OK;
   NLK_USE_DEVICE(c);
   hipLaunchKernelGGL(k_active_bytes_tagged, dim3((c->lazy_ngx + 255) / 256, c->lazy_ngy), dim3(256), 0, c->stream,
                      (const uint64_t*)c->chase.p + 64, c->lazy_dst ? c->lazy_dst : (uint8_t*)c->active.p, c->lazy_ngx);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->lazy_ngx = c->lazy_ngy = 0;
-  c->lazy_dst = nullptr;
+  nlk_set_lazy_active(c, 0, 0, nullptr);
   return NLK_OK;
 }
 
 int nlk_ctx_read_records(nlk_ctx* c, int* ngrid, int* kmax, int* gmax, unsigned char* active,
                          int* nsel, int* np0, int* nagg, unsigned int* topk,
                          unsigned int* gcoords) {
-  if (!c || !c->have_last) return fail(c, NLK_EINVAL, "no frame has been processed");
+  if (!c || !c->last.valid) return fail(c, NLK_EINVAL, "no frame has been processed");
   NLK_USE_DEVICE(c);
-  const NlkGeom& g = c->last;
+  const NlkGeom& g = c->last.g;
   const int n = g.ngx * g.ngy;
   if (ngrid) *ngrid = n;
   if (kmax) *kmax = g.kmax;

@@ -22,6 +22,15 @@ struct NlkBuf {
   void* base = nullptr;  // what hipMalloc returned (NLK_DEBUG_GUARD: p sits at the END of the allocation)
 };
 
+// the mask replay a group launch runs itself (k_group8m, NlkGTile::chase): bit planes, tagged decision words and
+// generation counter of the grid rows [0, rows); the launch's own first row is grid row row0
+struct NlkChase {
+  const uint32_t* planes = nullptr;
+  uint64_t* words = nullptr;
+  const uint32_t* gen = nullptr;
+  int reach = 0, row0 = 0, rows = 0;
+};
+
 // what a launcher works on: the stream and the per-target records of the patch-grid rows it is
 // given (the whole grid, a strip, or one band of a frame processed in bands on two streams)
 struct NlkRecView {
@@ -31,11 +40,7 @@ struct NlkRecView {
   uint32_t* gcoords = nullptr;   // [targets][gstride]
   uint64_t* marks = nullptr;     // [targets]
   uint32_t* wide = nullptr;      // [0] = queue length, then the queued targets (k_bm_wide)
-  // set by the frame call when the group kernel is to replay the processed mask itself (k_group8m, NlkGTile::chase)
-  const uint32_t* chase_planes = nullptr;
-  uint64_t* chase_words = nullptr;
-  const uint32_t* chase_gen = nullptr;
-  int chase_reach = 0, chase_row0 = 0, chase_rows = 0;
+  NlkChase chase;                // words != nullptr: the group kernel is to replay the processed mask itself
 };
 
 // The NLK_* environment switches (variants for comparison tests and experiments, none
@@ -75,12 +80,8 @@ struct nlk_ctx {
   hipStream_t stream = nullptr;
   hipStream_t aux_stream = nullptr;  // second stream of the banded frame pipeline (run_frame)
   hipEvent_t sync_ev[8] = {};        // cross-stream dependencies of that pipeline (no timing)
-  NlkRecView rv;                     // set by the orchestration before every launcher call
-  bool chase_on = false;             // the group launch being set up replays the mask itself ...
-  int chase_row0 = 0, chase_rows = 0;  // ... over the grid rows [0, chase_rows); the launch's first row is chase_row0
   int lazy_ngx = 0, lazy_ngy = 0;    // != 0: the decision bytes of the grid rows [0, lazy_ngy) are still to be expanded
   unsigned char* lazy_dst = nullptr; //        from the tagged words into this array (nlk_ctx_flush_active; read_records)
-  uint64_t* marks_ext = nullptr;     // strip calls: the matcher writes its mark words straight into the caller's array
   float* strip_acc = nullptr;        // strip calls: accumulator whose rows the layout kernel clears as it lays them out
   char err[512] = "";
   NlkBuf planes;                  // the planar copies of cur | prev | basic, one allocation (32-bit offsets between them: k_group8m.h)
@@ -111,11 +112,13 @@ struct nlk_ctx {
   NlkTvMail* tv_host = nullptr;   // pinned: the solver state, posted by the kernels (k_tvl1.h)
   unsigned tv_seq = 0;
   int tabs_psz = 0;
-  NlkGeom last{};
-  bool have_last = false;
-  const float *p_match = nullptr, *p_cur = nullptr, *p_prev = nullptr;  // planar images of the last match phase
-  const float* p_diff = nullptr;   // ... and of a smoother call: planar prev - cur (k_layout), else nullptr
-  bool layout_diff = false;        // the call being laid out keeps that image
+  // what a match call leaves for the group call that follows it: the geometry, the planar images and, of a smoother
+  // call, planar prev - cur (k_layout; else nullptr)
+  struct {
+    NlkGeom g;
+    const float *match, *cur, *prev, *diff;
+    bool valid;
+  } last{};
   // profiling: one set of NEV events per frame call, read back (and averaged)
   // only by nlk_ctx_get_timings, so the timed loop never synchronises
   static constexpr int NEV = 7, MAXSETS = 512;
@@ -177,25 +180,34 @@ static inline int reserve(nlk_ctx* c, NlkBuf& b, size_t bytes) {
   return NLK_OK;
 }
 
-// ---- launchers (one translation unit each; all enqueue on c->stream)
-// tu_group8.hip: the matrix-core / register group kernels for 8x8 patches
-int nlk_launch_group8(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev,
-                      float* acc, const uint8_t* active);
-// tu_groupp_{a,b,c}.hip: the packed-lane kernel (k_groupp.h), patch sizes 2..8 / 9..12 / 13..16, any channel count
-int nlk_launch_groupp_a(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev,
-                        float* acc, const uint8_t* active);
-int nlk_launch_groupp_b(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev,
-                        float* acc, const uint8_t* active);
-int nlk_launch_groupp_c(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev,
-                        float* acc, const uint8_t* active);
-// tu_group_generic.hip: the LDS-DCT kernel (k_group_lds.h), candidate lists of any length: its fixed shapes, patch
-// sizes 4 / 6 / 8 / 10 / 12 / 16 with 1 or 3 channels ...
-int nlk_launch_group_generic(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur,
+// the decision bytes of the grid rows [0, ngy) exist as tagged words only, until nlk_ctx_flush_active expands them
+// into `dst` (nullptr: the context's own array); ngx = 0: nothing awaits it
+static inline void nlk_set_lazy_active(nlk_ctx* c, int ngx, int ngy, unsigned char* dst) {
+  c->lazy_ngx = ngx;
+  c->lazy_ngy = ngy;
+  c->lazy_dst = dst;
+}
+static inline bool nlk_active_is_lazy(const nlk_ctx* c) { return c->lazy_ngx != 0; }
+
+// the shapes the tiled matchers (k_match.h) and the LDS-DCT group kernel (k_group_lds.h) are instantiated for
+static inline bool nlk_fixed_shape(int psz, int ch) {
+  return (psz == 4 || psz == 6 || psz == 8 || psz == 10 || psz == 12 || psz == 16) && (ch == 1 || ch == 3);
+}
+
+// ---- launchers (one translation unit each): every one enqueues on the view's stream and works on the view's
+// records; nothing about the call in progress is read from the context
+// the group launchers: `img` = the planar image the matcher saw, `cur` / `prev` = the planar frames, `active` = the
+// decisions of the view's rows
+typedef int NlkGroupLauncher(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float* img, const float* cur,
                              const float* prev, float* acc, const uint8_t* active);
-// ... and its run-time shape: patch sizes up to 32, any channel count with ch * psz^2 <= 4096
-int nlk_launch_group_any(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev,
-                         float* acc, const uint8_t* active);
+// tu_group8.hip: the matrix-core / register group kernels for 8x8 patches
+NlkGroupLauncher nlk_launch_group8;
+// tu_groupp_{a,b,c}.hip: the packed-lane kernel (k_groupp.h), patch sizes 2..8 / 9..12 / 13..16, any channel count
+NlkGroupLauncher nlk_launch_groupp_a, nlk_launch_groupp_b, nlk_launch_groupp_c;
+// tu_group_generic.hip: the LDS-DCT kernel (k_group_lds.h), candidate lists of any length: its fixed shapes
+// (nlk_fixed_shape) and its run-time shape: patch sizes up to 32, any channel count with ch * psz^2 <= 4096
+NlkGroupLauncher nlk_launch_group_generic, nlk_launch_group_any;
 // tu_match.hip: block matching + selection (wide = the queued targets of a temporal frame)
-int nlk_launch_match(nlk_ctx* c, const NlkGeom& g, const NlkTile& tl, size_t lds, const float* img,
+int nlk_launch_match(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const NlkTile& tl, size_t lds, const float* img,
                      int maxm, bool wide);
-int nlk_launch_match_generic(nlk_ctx* c, const NlkGeom& g, const float* img);
+int nlk_launch_match_generic(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float* img);

@@ -276,7 +276,7 @@ int enqueue_step(nlk_strips* S) {
     // (one call: where the group kernel can, it replays the mask rows down to the strip's last one inside its own
     // launch - the commit phase then reads as zero, its bit-plane kernel is counted with the groups)
     SCHK(S, T.c, nlk_dev_strip_commit_group(T.c, T.acc, T.marks_full, ngx, S->ngy, S->reach, T.p.gy0, T.active_full));
-    T.chased = T.c->lazy_ngx != 0;
+    T.chased = nlk_active_is_lazy(T.c);
     if ((rc = tick(T, PH_ACC))) return rc;
     // the accumulator rows written outside my own rows, packed for their owners
     if (T.h_top + T.h_bot > 0) {
@@ -602,7 +602,7 @@ int nlk_strips_own_rows(nlk_strips* S, int local, int* y0, int* y1, float** rows
     // rows [0, its last row) are written now - the whole grid for the last strip; a replayed HIP graph never came
     // through the call that would have noted it, hence from the strip's own flag)
     if (T.chased) {
-      T.c->lazy_ngx = S->ngx; T.c->lazy_ngy = T.p.gy0 + T.rows; T.c->lazy_dst = T.active_full;
+      nlk_set_lazy_active(T.c, S->ngx, T.p.gy0 + T.rows, T.active_full);
       HIPCHK(T.c, hipSetDevice(T.device));
       int rc = nlk_ctx_flush_active(T.c);
       if (rc) return rc;

@@ -10,7 +10,7 @@ const void* nlk_group8m_ilp_kernel(int ch, bool smoother, int sep);  // tu_group
 namespace {
 
 template <int CH, bool SMO>
-int launch_group8_t(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur,
+int launch_group8_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float* img, const float* cur,
                     const float* prev, float* acc, const uint8_t* active) {
   constexpr int PSZ = 8;
   // psz 8 runs its DCTs on the matrix cores (k_group8m.h); NLK_GROUP_DPP selects the
@@ -46,16 +46,16 @@ int launch_group8_t(nlk_ctx* c, const NlkGeom& g, const float* img, const float*
     const float* hi = lo + c->planes.cap / sizeof(float);
     const bool inside = img >= lo && img < hi && cur >= lo && cur < hi && (!prev || (prev >= lo && prev < hi));
     if (!inside || c->planes.cap >= ((size_t)1 << 32)) {
-      if (c->rv.chase_words) return fail(c, NLK_EINVAL, "internal: mask replay handed to a group kernel that cannot run it");
-      return nlk_launch_groupp_a(c, g, img, cur, prev, acc, active);
+      if (v.chase.words) return fail(c, NLK_EINVAL, "internal: mask replay handed to a group kernel that cannot run it");
+      return nlk_launch_groupp_a(c, v, g, img, cur, prev, acc, active);
     }
   }
-  if (mfma && SMO && prev && !(c->p_diff && cur == c->p_cur && prev == c->p_prev)) {
+  if (mfma && SMO && prev && !(c->last.diff && cur == c->last.cur && prev == c->last.prev)) {
     // (the smoother's pass B reads the difference image the layout kernel made of exactly these two images)
-    if (c->rv.chase_words) return fail(c, NLK_EINVAL, "internal: mask replay handed to a group kernel that cannot run it");
-    return nlk_launch_groupp_a(c, g, img, cur, prev, acc, active);
+    if (v.chase.words) return fail(c, NLK_EINVAL, "internal: mask replay handed to a group kernel that cannot run it");
+    return nlk_launch_groupp_a(c, v, g, img, cur, prev, acc, active);
   }
-  if (c->rv.chase_words && (!mfma || c->deterministic))
+  if (v.chase.words && (!mfma || c->deterministic))
     return fail(c, NLK_EINVAL, "internal: mask replay handed to a group kernel that cannot run it");
   if (c->deterministic && !mfma)
     return fail(c, NLK_EUNSUP, "deterministic aggregation is not available in the NLK_GROUP_DPP variant");
@@ -67,16 +67,16 @@ int launch_group8_t(nlk_ctx* c, const NlkGeom& g, const float* img, const float*
     NlkGTile tl{};
     tl.pbase = (const float*)c->planes.p;
     // (the smoother's pass B transforms previous - image: laid out once per call by k_layout; `cur` is what gets filtered)
-    tl.diff = (SMO && prev) ? c->p_diff : nullptr;
+    tl.diff = (SMO && prev) ? c->last.diff : nullptr;
     tl.split = split;
     tl.far = pass;
-    tl.chase = c->rv.chase_words ? c->rv.chase_reach : 0;
+    tl.chase = v.chase.words ? v.chase.reach : 0;
     tl.chase_test_skip0 = nlk_set(c->sw.chase_test_skip0);
-    tl.chase_gen = c->rv.chase_gen;
-    tl.chase_row0 = c->rv.chase_row0;
-    tl.chase_rows = c->rv.chase_rows;
-    tl.chase_planes = c->rv.chase_planes;
-    tl.chase_words = c->rv.chase_words;
+    tl.chase_gen = v.chase.gen;
+    tl.chase_row0 = v.chase.row0;
+    tl.chase_rows = v.chase.rows;
+    tl.chase_planes = v.chase.planes;
+    tl.chase_words = v.chase.words;
     // LDS tile halo = reach of the dominant kind of group; without the split the rare spatial-branch
     // groups of a temporal frame that reach further fall back to HBM atomics
     tl.wmax = (g.smoother || g.have_prev) ? g.wsz_t : g.wsz_x;
@@ -168,7 +168,7 @@ int launch_group8_t(nlk_ctx* c, const NlkGeom& g, const float* img, const float*
     const size_t cnt_off = (nflag + 15) & ~(size_t)15, cnt_bytes = sizeof(int) * ncnt;
     int rc;
     if ((rc = reserve(c, c->slab, sizeof(float) * need)) || (rc = reserve(c, c->tflag, cnt_off + cnt_bytes))) return rc;
-    HIPCHK(c, hipMemsetAsync((uint8_t*)c->tflag.p + cnt_off, 0, cnt_bytes, c->rv.stream));
+    HIPCHK(c, hipMemsetAsync((uint8_t*)c->tflag.p + cnt_off, 0, cnt_bytes, v.stream));
     for (int pass = 0; pass < npass; ++pass) {
       tls[pass].slab = (float*)c->slab.p + slab_at[pass];
       tls[pass].tflag = (uint8_t*)c->tflag.p + flag_at[pass];
@@ -194,12 +194,12 @@ int launch_group8_t(nlk_ctx* c, const NlkGeom& g, const float* img, const float*
     HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds));
     const float* basis = (const float*)c->tabs.p;
-    hipLaunchKernelGGL(kern, dim3(mfma ? tl.nmain + ((tl.single * g.ngx + 7) / 8) * 8 : nlk_xcd_grid(tl.ntx * tl.nty)), dim3(64), lds, c->rv.stream, img, cur, prev,
-                       (const uint8_t*)c->vmap.p, g, tl, (const uint32_t*)c->rv.topk,
-                       (const NlkTarget*)c->rv.tinfo, (const uint32_t*)c->rv.gcoords,
+    hipLaunchKernelGGL(kern, dim3(mfma ? tl.nmain + ((tl.single * g.ngx + 7) / 8) * 8 : nlk_xcd_grid(tl.ntx * tl.nty)), dim3(64), lds, v.stream, img, cur, prev,
+                       (const uint8_t*)c->vmap.p, g, tl, (const uint32_t*)v.topk,
+                       (const NlkTarget*)v.tinfo, (const uint32_t*)v.gcoords,
                        active, basis, basis + PSZ * PSZ, acc);
     if (c->deterministic)
-      nlk_launch_gather(c->rv.stream, acc, tl.slab, tl.tflag, tl.tcount, g, tl, CH + 1);
+      nlk_launch_gather(v.stream, acc, tl.slab, tl.tflag, tl.tcount, g, tl, CH + 1);
     HIPCHK(c, hipGetLastError());
   }
   return NLK_OK;
@@ -207,12 +207,12 @@ int launch_group8_t(nlk_ctx* c, const NlkGeom& g, const float* img, const float*
 
 }  // namespace
 
-int nlk_launch_group8(nlk_ctx* c, const NlkGeom& g, const float* img, const float* cur, const float* prev,
+int nlk_launch_group8(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float* img, const float* cur, const float* prev,
                       float* acc, const uint8_t* active) {
 #define NLK_FAST(C)                                                                  \
   if (g.ch == C)                                                                     \
-    return g.smoother ? launch_group8_t<C, true>(c, g, img, cur, prev, acc, active)  \
-                      : launch_group8_t<C, false>(c, g, img, cur, prev, acc, active);
+    return g.smoother ? launch_group8_t<C, true>(c, v, g, img, cur, prev, acc, active)  \
+                      : launch_group8_t<C, false>(c, v, g, img, cur, prev, acc, active);
   NLK_FAST(1) NLK_FAST(3)
 #undef NLK_FAST
   return fail(c, NLK_EUNSUP, "%d channels not supported (1 or 3)", g.ch);
