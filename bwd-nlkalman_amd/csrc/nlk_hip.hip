@@ -80,6 +80,7 @@ int launch_group(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float*
   // instantiated (nlk_fixed_shape) and its run-time shape (patch size and channel count from NlkGeom) otherwise, as
   // patches above 16 do
   const bool lists_fit = g.kmax <= 128 && g.gstride <= 128;
+  memset(c->group_shape, 0, sizeof c->group_shape);  // (nlk_ctx_last_group_shape: "another launcher ran", until tu_group8.hip says otherwise)
   if (g.psz > 16) return nlk_launch_group_any(c, v, g, img, cur, prev, acc, active);  // (GroupAny: 17..32)
   if (nlk_set(c->sw.generic_group) || !lists_fit)
     return nlk_fixed_shape(g.psz, g.ch) ? nlk_launch_group_generic(c, v, g, img, cur, prev, acc, active)
@@ -269,6 +270,12 @@ int nlk_ctx_reload_switches(nlk_ctx* c) {
       x->sw.load();
       if (nlk_set(x->sw.deterministic)) x->deterministic = x->sw.deterministic != 0;
     }
+  return NLK_OK;
+}
+
+int nlk_ctx_last_group_shape(nlk_ctx* c, int out[12]) {
+  if (!c || !out) return fail(c, NLK_EINVAL, "null context / output");
+  memcpy(out, c->group_shape, sizeof c->group_shape);
   return NLK_OK;
 }
 

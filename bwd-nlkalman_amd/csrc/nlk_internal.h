@@ -119,6 +119,7 @@ struct nlk_ctx {
     const float *match, *cur, *prev, *diff;
     bool valid;
   } last{};
+  int group_shape[12] = {};  // nlk_ctx_last_group_shape: written after a group launch is enqueued, read by nothing else
   // profiling: one set of NEV events per frame call, read back (and averaged)
   // only by nlk_ctx_get_timings, so the timed loop never synchronises
   static constexpr int NEV = 7, MAXSETS = 512;

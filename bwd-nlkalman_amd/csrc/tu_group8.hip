@@ -62,6 +62,8 @@ int launch_group8_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const flo
   // Deterministic mode runs a temporal frame's far-reaching (spatial-branch) groups in a second
   // launch whose tiles have the spatial halo, so that no member ever leaves its tile (k_group8.h)
   const bool split = c->deterministic && g.have_prev && !g.smoother && g.wsz_x > g.wsz_t;
+  if (nlk_or(c->sw.gtx, 1) < 1 || nlk_or(c->sw.gty, 1) < 1)
+    return fail(c, NLK_EUNSUP, "NLK_GTX / NLK_GTY: a tile holds at least 1 x 1 targets");
   // the tiles of a pass: halo, targets per tile, LDS strides
   auto shape = [&](int pass) {
     NlkGTile tl{};
@@ -151,6 +153,11 @@ int launch_group8_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const flo
   };
   const int npass = split ? 2 : 1;
   NlkGTile tls[2] = {shape(0), shape(split ? 1 : 0)};
+  // (a tile's target records sit one per lane of its wavefront, and both kernels read them back by lane number; the
+  // LDS limit below would let a 65 x 1 tile through)
+  for (int pass = 0; pass < npass; ++pass)
+    if ((long)tls[pass].tgx * tls[pass].tgy > 64)
+      return fail(c, NLK_EUNSUP, "%d x %d targets per tile: at most 64, one per lane", tls[pass].tgx, tls[pass].tgy);
   // Deterministic mode: slabs, "written" flags and tile-row counters of BOTH passes, sized from each pass's OWN
   // tiles before the first launch (growing a buffer frees it). (Round 3 sized the far pass with the near pass's
   // tile rows - half as many since the near tiles hold two grid rows - and its counters likewise: writes past
@@ -202,6 +209,11 @@ int launch_group8_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const flo
       nlk_launch_gather(v.stream, acc, tl.slab, tl.tflag, tl.tcount, g, tl, CH + 1);
     HIPCHK(c, hipGetLastError());
   }
+  // what ran, for nlk_ctx_last_group_shape (include/nlk_hip.h); nothing reads it back on a launch path
+  const NlkGTile& t0 = tls[0];
+  const int report[12] = {mfma ? NLK_GROUP_FAMILY_8M : NLK_GROUP_FAMILY_8, sep, t0.tgx, t0.tgy, t0.ntx, t0.nty,
+                          t0.nty_full, t0.single, npass, t0.chase, split ? tls[1].tgx : 0, split ? tls[1].tgy : 0};
+  memcpy(c->group_shape, report, sizeof report);
   return NLK_OK;
 }
 

@@ -292,16 +292,21 @@ def test_gpu_strips_match_oracle_strips(ctx, built, O, synth, world):
     cases.assert_close(got, want, f"{world} strips on the GPU vs on the oracle")
 
 
-@pytest.mark.parametrize("fused", [False, True])
-@pytest.mark.parametrize("world", [2, 4])
-def test_gpu_exact_strips_equal_whole_frame(ctx, built, O, synth, world, fused):
+@pytest.mark.parametrize("world,fused,shape", [pytest.param(n, f, s, id=f"{n}-{f}" + (f"-{s}" if s else ""))
+                                               for s in (None, "3x2") for f in (False, True) for n in (2, 4)])
+def test_gpu_exact_strips_equal_whole_frame(ctx, built, O, synth, monkeypatch, world, fused, shape):
     """The three-phase strip form (match per strip -> concatenated mark words ->
     whole-grid mask replay -> group per strip), i.e. what N ranks do in exact
     mode, run sequentially on one GPU: must equal the whole-frame call. `fused`: phases 2 + 3 of a strip as
     one call (nlk_dev_strip_commit_group: the replay of the rows down to the strip's last one inside the group
-    kernel's launch, what csrc/strips.hip enqueues) instead of mask_commit + strip_group."""
+    kernel's launch, what csrc/strips.hip enqueues) instead of mask_commit + strip_group. `shape` "3x2": the group
+    tiles of a full-size frame (two grid rows each, with their one-row tiles and single targets at the end) - in the
+    fused form they index the decision words of a strip that does not start at grid row 0."""
     import importlib
     strips = importlib.import_module("bwd-nlkalman_amd.strips")
+    if shape:
+        monkeypatch.setenv("NLK_GTX", shape[0])
+        monkeypatch.setenv("NLK_GTY", shape[2])
     w, h, ch, sigma = 96, 128, 3, 20.0
     n0, n1, _ = synth.noisy_pair(w, h, ch, sigma, 33)
     o0, o1 = O.rgb2opp(n0), O.rgb2opp(n1)
@@ -334,6 +339,10 @@ def test_gpu_exact_strips_equal_whole_frame(ctx, built, O, synth, world, fused):
             ctx.free(d_scratch)
         else:
             ctx.strip_group(d_acc, d_active + s["gy0"] * ngx)
+        if shape:  # (the forced tiles are what ran, with the replay inside the launch exactly in the fused form)
+            ran = ctx.last_group_shape()
+            assert (ran["family"], ran["tgx"], ran["tgy"]) == ("k_group8m", 3, 2), ran
+            assert (ran["chase"] > 0) == fused and ran["ntx"] == (ngx + 2) // 3, ran
         acc[:, s["Y0"]:s["Y1"]] += ctx.download(d_acc, (ch + 1, hl, w))
         for x in (d_cur, d_prev, d_acc):
             ctx.free(x)
@@ -901,6 +910,40 @@ def test_smoother_full_size_1080p(ctx, built, O, synth):
     cases.assert_close(g, r, "smo 1080p")
 
 
+def _random_config(rng, built, psz):
+    """The next configuration of the randomised tests for patch size `psz`: (smoother, cur, prev, basic, sigma,
+    params, description). Odd image sizes, clipped windows, k larger than the window, group sizes above k, NaN holes,
+    second-iteration and smoother calls."""
+    step = psz // 2
+    ch = int(rng.choice([1, 3]))
+    w = int(rng.integers(psz, int(os.environ.get("NLK_RANDOM_MAXW", 90))))
+    h = int(rng.integers(psz, int(os.environ.get("NLK_RANDOM_MAXH", 70))))
+    smoother = rng.random() < 0.25
+    wsz_t = int(rng.integers(1, min(15, 3 * step + step - 1) + 1))
+    wsz_x = int(rng.integers(1, min(15, 3 * step + step - 1) + 1))
+    npx, npt = int(rng.integers(2, 70)), int(rng.integers(2, 70))
+    ntagg = int(rng.integers(1, 45))
+    over = dict(patch_sz=psz, search_sz_x=wsz_x, search_sz_t=wsz_t, npatches_x=npx, npatches_t=npt,
+                npatches_tagg=ntagg)
+    mode = built.SMO1 if smoother else int(rng.choice([built.FLT1, built.FLT2]))
+    sigma = float(rng.choice([10.0, 20.0, 40.0]))
+    p = built.default_params(sigma, mode, **over)
+    cur = rng.uniform(0, 255, (h, w, ch)).astype(np.float32)
+    kind = rng.integers(0, 3) if not smoother else rng.integers(1, 3)
+    prev = None
+    if kind >= 1:
+        prev = (cur + rng.normal(0, 8, cur.shape)).astype(np.float32)
+    if kind == 2:
+        y0, x0 = int(rng.integers(0, h)), int(rng.integers(0, w))
+        prev[y0:y0 + int(rng.integers(1, 9)), x0:x0 + int(rng.integers(1, 9)), :] = np.nan
+        prev[:, :1, :] = np.nan
+    basic = None
+    if not smoother and mode == built.FLT2:
+        basic = (cur + rng.normal(0, 3, cur.shape)).astype(np.float32)
+    what = f"{w}x{h}x{ch} psz{psz} sx{wsz_x} st{wsz_t} nx{npx} nt{npt} na{ntagg} mode{mode} prev{kind} sigma{sigma}"
+    return smoother, cur, prev, basic, sigma, p, what
+
+
 @pytest.mark.parametrize("launch", ["auto", "large-grid", "large-grid-4x2"])
 def test_randomised_parameters_and_shapes(ctx, built, O, monkeypatch, launch):
     """120 seeded random configurations: odd image sizes, every supported patch
@@ -923,32 +966,7 @@ def test_randomised_parameters_and_shapes(ctx, built, O, monkeypatch, launch):
         if done == want:
             break
         psz = int(rng.choice([4, 6, 8, 8, 8, 10, 12, 12, 16]))
-        step = psz // 2
-        ch = int(rng.choice([1, 3]))
-        w = int(rng.integers(psz, int(os.environ.get("NLK_RANDOM_MAXW", 90))))
-        h = int(rng.integers(psz, int(os.environ.get("NLK_RANDOM_MAXH", 70))))
-        smoother = rng.random() < 0.25
-        wsz_t = int(rng.integers(1, min(15, 3 * step + step - 1) + 1))
-        wsz_x = int(rng.integers(1, min(15, 3 * step + step - 1) + 1))
-        npx, npt = int(rng.integers(2, 70)), int(rng.integers(2, 70))
-        ntagg = int(rng.integers(1, 45))
-        over = dict(patch_sz=psz, search_sz_x=wsz_x, search_sz_t=wsz_t, npatches_x=npx, npatches_t=npt,
-                    npatches_tagg=ntagg)
-        mode = built.SMO1 if smoother else int(rng.choice([built.FLT1, built.FLT2]))
-        sigma = float(rng.choice([10.0, 20.0, 40.0]))
-        p = built.default_params(sigma, mode, **over)
-        cur = rng.uniform(0, 255, (h, w, ch)).astype(np.float32)
-        kind = rng.integers(0, 3) if not smoother else rng.integers(1, 3)
-        prev = None
-        if kind >= 1:
-            prev = (cur + rng.normal(0, 8, cur.shape)).astype(np.float32)
-        if kind == 2:
-            y0, x0 = int(rng.integers(0, h)), int(rng.integers(0, w))
-            prev[y0:y0 + int(rng.integers(1, 9)), x0:x0 + int(rng.integers(1, 9)), :] = np.nan
-            prev[:, :1, :] = np.nan
-        basic = None
-        if not smoother and mode == built.FLT2:
-            basic = (cur + rng.normal(0, 3, cur.shape)).astype(np.float32)
+        smoother, cur, prev, basic, sigma, p, what = _random_config(rng, built, psz)
         fn = O.smooth_frame if smoother else O.filter_frame
         r, tr = fn(cur, prev, basic, sigma, _to_o(O, p), trace=True)
         try:
@@ -956,8 +974,7 @@ def test_randomised_parameters_and_shapes(ctx, built, O, monkeypatch, launch):
         except built.NlkError as e:  # combinations the kernels reject loudly (reach > 3)
             assert "reach" in str(e) or "LDS" in str(e), str(e)
             continue
-        what = f"random #{it}: {w}x{h}x{ch} psz{psz} sx{wsz_x} st{wsz_t} nx{npx} nt{npt} na{ntagg} " \
-               f"mode{mode} prev{kind} sigma{sigma}"
+        what = f"random #{it}: {what}"
         _check_records(rec, tr, what)
         # a pixel whose summed weight sits AT the reference's absolute threshold (aggr > 1e-6 ?
         # normalise : pass the input through, src/nlkalman.c:939-942) may fall on either side with
