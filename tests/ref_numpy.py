@@ -3,7 +3,8 @@
 using scipy.fft.dctn(type=2, norm='ortho') for the transform (the published
 definition FFTW's REDFT10 + the reference's scaling amount to; reference:
 src/nlkalman.c:204-220, 281-298). Pure-Python loops: small frames only.
-Used by tests/test_oracle.py to cross-check the C oracle."""
+Used by tests/test_oracle.py to cross-check the C oracle and by tests/test_gain_regimes.py as the float64 reference
+of the group kernels' statistics, gains and weights."""
 import numpy as np
 from scipy.fft import dctn, idctn
 
@@ -28,7 +29,9 @@ def _idct(p):
     return idctn(p.astype(np.float64), type=2, norm="ortho", axes=(1, 2)).astype(np.float32)
 
 
-def frame(cur, prev, basic, sigma, P, smoother=False):
+def frame(cur, prev, basic, sigma, P, smoother=False, trace=False):
+    """trace=True: returns (frame, {"aggr": the weight plane summed in float64 - 1 / max(vp, 1e-6) in float64 times
+    the window, "vp": the float64 vp of every target in grid order, NaN where the mask skipped it})."""
     f32 = np.float32
     h, w, ch = cur.shape
     psz, step = P["patch_sz"], P["patch_sz"] // 2
@@ -36,6 +39,8 @@ def frame(cur, prev, basic, sigma, P, smoother=False):
     match = basic if basic is not None else cur
     out = np.zeros_like(cur)
     aggr = np.zeros((h, w), f32)
+    aggr64 = np.zeros((h, w), np.float64)
+    vps = []
     mask = np.zeros((h, w), np.int32)
     W = window(psz)
     ntagg = P["npatches_tagg"]
@@ -46,6 +51,7 @@ def frame(cur, prev, basic, sigma, P, smoother=False):
     for py in range(0, h - psz + 1, step):
         for px in range(0, w - psz + 1, step):
             if mask[py, px]:
+                vps.append(np.nan)
                 continue
             prev_p = valid(px, py)
             k = P["npatches_t"] if prev_p else P["npatches_x"]
@@ -124,6 +130,8 @@ def frame(cur, prev, basic, sigma, P, smoother=False):
                 groups = [(px, py, _patch(cur, px, py, psz))]
                 vp = 0.0
             wgt = f32(1.0) / f32(vp if vp > 1e-6 else 1e-6)  # (the macro of src/nlkalman.c:15-18, :1824: a NaN vp gives 1e-6)
+            vps.append(float(vp))
+            wgt64 = 1.0 / (float(vp) if vp > 1e-6 else 1e-6)
             if smoother:
                 mark = 1 if np0 else 0
             else:
@@ -131,8 +139,11 @@ def frame(cur, prev, basic, sigma, P, smoother=False):
             for (qx, qy, g) in groups:
                 ww = (wgt * W).astype(f32)
                 aggr[qy:qy + psz, qx:qx + psz] += ww
+                aggr64[qy:qy + psz, qx:qx + psz] += wgt64 * W.astype(np.float64)
                 out[qy:qy + psz, qx:qx + psz, :] += np.transpose(ww[None] * g, (1, 2, 0)).astype(f32)
                 mask[qy, qx] += mark
     ok = aggr > 1e-6
     res = np.where(ok[:, :, None], out / np.where(ok, aggr, 1)[:, :, None], cur)
+    if trace:
+        return res.astype(f32), {"aggr": aggr64, "vp": np.array(vps, np.float64)}
     return res.astype(f32)
