@@ -30,7 +30,7 @@ HIP_SYMBOLS = [
     "nlk_dev_strip_match", "nlk_dev_strip_match_rows", "nlk_dev_mask_commit", "nlk_dev_strip_group",
     "nlk_tvl1_default_params", "nlk_tvl1_scales", "nlk_dev_tvl1_flow", "nlk_dev_gray",
     "nlk_dev_occlusion_mask", "nlk_dev_image_dct", "nlk_dev_copy_block", "nlk_host_tables", "nlk_ctx_set_deterministic", "nlk_dev_zero", "nlk_dev_add", "nlk_dev_copy_peer",
-    "nlk_filter_frame_host", "nlk_smooth_frame_host", "nlk_dev_strip_match_part", "nlk_ctx_reload_switches", "nlk_ctx_last_group_shape", "nlk_ctx_set_strip_accumulator",
+    "nlk_filter_frame_host", "nlk_smooth_frame_host", "nlk_dev_strip_match_part", "nlk_ctx_reload_switches", "nlk_ctx_last_group_shape", "nlk_ctx_last_group_packed", "nlk_host_packed_entry", "nlk_ctx_count_packed", "nlk_ctx_set_strip_accumulator",
     "nlk_strips_create", "nlk_strips_destroy", "nlk_strips_last_error", "nlk_rccl_unique_id", "nlk_strips_rccl_init",
     "nlk_strips_transport", "nlk_strips_load", "nlk_strips_set_options", "nlk_strips_step", "nlk_strips_sync",
     "nlk_strips_own_rows", "nlk_strips_ctx", "nlk_strips_geometry", "nlk_strips_stats", "nlk_strips_set_dry_run",
@@ -239,6 +239,9 @@ def hip():
         L.nlk_ctx_set_deterministic.argtypes = [vp, i]
         L.nlk_ctx_reload_switches.argtypes = [vp]
         L.nlk_ctx_last_group_shape.argtypes = [vp, C.POINTER(i)]
+        L.nlk_ctx_last_group_packed.argtypes = [vp]
+        L.nlk_host_packed_entry.argtypes = [i, i, i, i, i, i, i, C.POINTER(C.c_uint), C.POINTER(i)]
+        L.nlk_ctx_count_packed.argtypes = [vp, C.POINTER(i)]
         L.nlk_ctx_set_strip_accumulator.argtypes = [vp, vp]
         L.nlk_strips_create.argtypes = [C.POINTER(vp), i, C.POINTER(i), i, i, i, i, i, C.c_float, C.POINTER(Params), i, i]
         L.nlk_strips_destroy.argtypes = [vp]
@@ -456,6 +459,16 @@ def host_tables(psz):
     return b, w, b12
 
 
+def host_packed_entry(dx, dy, r, k=1, px=16, py=16, passthrough=False):
+    """(byte, (x, y) decoded from it) of one entry of the packed candidate / member lists: displacement (dx, dy) from a
+    target at (px, py) that searched radius r and kept k candidates - through the functions the matcher and the group
+    kernel call (nlk_host_packed_entry; no device needed); None where a packed record cannot hold it."""
+    byte, back = C.c_uint(0), (C.c_int * 2)()
+    if hip().nlk_host_packed_entry(px, py, dx, dy, r, k, int(passthrough), C.byref(byte), back):
+        return None
+    return byte.value, (back[0], back[1])
+
+
 def reload_switches():
     """Re-read the NLK_* environment switches for every live context of this process (they are read once,
     at context creation: include/nlk_hip.h). Only the tests need this."""
@@ -512,14 +525,23 @@ class Context:
     def last_group_shape(self):
         """What the last group launch ran (nlk_ctx_last_group_shape): family "k_group8m" / "k_group8" / None (another
         launcher), sep, tgx, tgy, ntx, nty, nty_full, single, passes, chase (reach of the replay inside the launch, 0 =
-        not in it), far = (tgx, tgy) of deterministic mode's far pass or None."""
+        not in it), far = (tgx, tgy) of deterministic mode's far pass or None, packed_lists / packed_far = the launch / its far
+        pass read the lists packed (nlk_ctx_last_group_packed)."""
         out = (C.c_int * 12)()
         self._chk(self.L.nlk_ctx_last_group_shape(self.h, out))
         v = list(out)
         d = dict(zip(("sep", "tgx", "tgy", "ntx", "nty", "nty_full", "single", "passes", "chase"), v[1:10]))
         d["family"] = {1: "k_group8m", 2: "k_group8"}.get(v[0])
         d["far"] = (v[10], v[11]) if v[8] > 1 else None
+        pk = self.L.nlk_ctx_last_group_packed(self.h)
+        d["packed_lists"], d["packed_far"] = pk > 0 and bool(pk & 1), pk > 0 and bool(pk & 2)
         return d
+
+    def count_packed(self):
+        """Targets of the last match phase with a valid packed record (nlk_ctx_count_packed)."""
+        n = C.c_int()
+        self._chk(self.L.nlk_ctx_count_packed(self.h, C.byref(n)))
+        return n.value
 
     def set_profiling(self, on):
         self._chk(self.L.nlk_ctx_set_profiling(self.h, int(on)))

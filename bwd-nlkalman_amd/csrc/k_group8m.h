@@ -228,7 +228,14 @@ template <int CH, int SEP> constexpr int nlk_g8_stash_floats() {
 #endif
 // (UNIT: which translation unit instantiated the kernel - the same source compiled under two instruction schedulers,
 // tu_group8.hip and tu_group8_ilp.hip; it changes nothing but the symbol)
-template <int CH, bool SMO, int SEP, int UNIT = 0>
+// PK: the packed-list instantiation (nlk_common.h; tu_group8.hip selects it per launch: the lists of the call's
+// dominant targets of at most 32 entries, no list above 64, at most 8 targets per tile). A tile's lists arrive with its records - lane 8 tt + j loads word j of target
+// tt's candidates and word j of its members, two coalesced loads per TILE, requested before the tile is cleared - and
+// a target's entries come out of those two registers by one ds_bpermute each: no target starts by waiting for a
+// global round trip. With lists of at most 32 entries the second 64-entry round of every per-lane list register
+// (NR = 1 below) goes away with its selects. A target whose record is not valid (flag clear: a wide-window target of
+// a temporal frame) loads its 32-bit lists as the other instantiation does, under a wave-uniform branch.
+template <int CH, bool SMO, int SEP, int UNIT = 0, bool PK = false>
 __global__ void __launch_bounds__(64, NLK_G8_WPS)
 k_group8m(const float* __restrict__ img,   // matching / statistics image (planar)
           const float* __restrict__ cur,   // image whose patches are filtered
@@ -301,7 +308,28 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
   const uint64_t* chase_wp = tl.chase_words;
   uint64_t chase_v = 0;
   bool chase_late = false;
-  uint32_t rec_vb[4] = {0u, 0u, 0u, 0u};
+  constexpr int NR = PK ? 1 : 2;  // rounds of 64 list entries a target may have
+  uint32_t rec_vb[2 * NR];
+#pragma unroll
+  for (int i = 0; i < 2 * NR; ++i) rec_vb[i] = 0u;
+  auto rec_vb_any = [&]() {
+    uint32_t a = rec_vb[0] | rec_vb[1];
+    if constexpr (NR > 1) a |= rec_vb[2] | rec_vb[3];
+    return a;
+  };
+  // (PK) word (lane & 7) of the candidates / members of target lane >> 3. The list lengths (at most 32) and the
+  // flags of a target share ONE register there, rec_nsel = nsel | nagg << 8 | flags << 16: the records of a tile stay
+  // in registers over all its targets, and the packed form must not cost more of them than it frees
+  uint32_t pk_c = 0u, pk_g = 0u;
+  if constexpr (PK) {
+    const int ptt = lane >> 3;
+    if (ptt < cx * cy) {
+      const int ty = ptt / cx, tx = ptt - ty * cx;
+      const uint32_t* rec = tinfo[(size_t)(gy0 + ty) * g.ngx + gx0 + tx].pl + (lane & 7);
+      pk_c = rec[0];
+      pk_g = rec[8];
+    }
+  }
   if (lane < cx * cy) {
     const int ty = lane / cx, tx = lane - ty * cx;
     const size_t t = (size_t)(gy0 + ty) * g.ngx + gx0 + tx;
@@ -327,9 +355,10 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
       rec_act = active[t];
     }
     const NlkTarget info = tinfo[t];
-    rec_nsel = info.nsel; rec_nagg = info.nagg;
+    if constexpr (PK) rec_nsel = info.nsel | (info.nagg << 8) | (info.flags << 16);
+    else { rec_nsel = info.nsel; rec_nagg = info.nagg; }
     rec_vb[0] = (uint32_t)info.vbits[0]; rec_vb[1] = (uint32_t)(info.vbits[0] >> 32);
-    rec_vb[2] = (uint32_t)info.vbits[1]; rec_vb[3] = (uint32_t)(info.vbits[1] >> 32);
+    if constexpr (NR > 1) { rec_vb[2] = (uint32_t)info.vbits[1]; rec_vb[3] = (uint32_t)(info.vbits[1] >> 32); }
   }
   if (tl.chase) {
     if (__ballot(chase_late)) {  // (wave-uniform) self-rescue: the rows down to this tile's last one
@@ -342,8 +371,8 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
     if (lane < cx * cy) rec_act = ((uint32_t)chase_v >> chase_bit) & 1u;
   }
   if (tl.split) {  // (the two launches of deterministic mode: most tiles of the far one have nothing to do)
-    const bool work = rec_act && rec_nagg != 0 &&
-                      nlk_far_target(g, (rec_vb[0] | rec_vb[1] | rec_vb[2] | rec_vb[3]) ? 1 : 0) == (tl.far != 0);
+    const bool work = rec_act && (PK ? (rec_nsel & 0xff00) : rec_nagg) != 0 &&
+                      nlk_far_target(g, rec_vb_any() ? 1 : 0) == (tl.far != 0);
     if (!__ballot(work)) {
       if (threadIdx.x == 0) tl.tflag[tile_id] = 0;
       return;
@@ -436,36 +465,60 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
 
   for (int tt = 0; tt < cx * cy; ++tt) {
     if (!__builtin_amdgcn_readlane(rec_act, tt)) continue;
-    const int nagg = __builtin_amdgcn_readlane(rec_nagg, tt);
+    const int rec_tt = __builtin_amdgcn_readlane(rec_nsel, tt);  // (PK: lengths and flags in one word)
+    const int nagg = PK ? (rec_tt >> 8) & 0xff : __builtin_amdgcn_readlane(rec_nagg, tt);
     if (nagg == 0) continue;
     if (tl.split) {  // (deterministic mode: near and far groups in separate launches)
-      const uint32_t anyv = (uint32_t)__builtin_amdgcn_readlane((int)(rec_vb[0] | rec_vb[1] | rec_vb[2] | rec_vb[3]), tt);
+      const uint32_t anyv = (uint32_t)__builtin_amdgcn_readlane((int)rec_vb_any(), tt);
       if (nlk_far_target(g, anyv ? 1 : 0) != (tl.far != 0)) continue;
     }
     any_target = true;
     const int ty = tt / cx, tx = tt - ty * cx;
     const size_t t = (size_t)(gy0 + ty) * g.ngx + gx0 + tx;
-    const int k = __builtin_amdgcn_readlane(rec_nsel, tt);
+    const int k = PK ? rec_tt & 0xff : rec_tt;
 
     // candidate / member lists: one entry per lane (two rounds); validity and
     // group-membership bits of the candidates as wave-uniform masks
-    uint32_t qreg[2], greg[2];
-    uint64_t vbits[2], gbits[2];
+    uint32_t qreg[NR], greg[NR];
+    uint64_t vbits[NR], gbits[NR];
+    // entry i (wave-uniform) of a pair of 64-entry words / its word
+    auto word_of = [&](const auto& a, int i) {
+      if constexpr (NR > 1) return i < 64 ? a[0] : a[1];
+      else return a[0];
+    };
+    bool unpacked = true;
+    if constexpr (PK) {
+      const int fl = rec_tt >> 16;
+      if (fl & NLK_TF_PACKED) {  // (wave-uniform)
+        // entry `lane` of both lists: byte lane & 3 of word lane >> 2 of this target, held by lane 8 tt + (lane >> 2);
+        // the displacement from the target's own position back to a frame coordinate, as the matcher stored it
+        unpacked = false;
+        const int r = nlk_target_radius(g, fl & 1);
+        const int px = (gx0 + tx) * step, py = g.oy + (gy0 + ty) * step;
+        const int srcl = 8 * tt + ((lane >> 2) & 7), sh = 8 * (lane & 3);
+        const uint32_t bc = (nlk_bperm_u(pk_c, srcl) >> sh) & 0xffu, bg = (nlk_bperm_u(pk_g, srcl) >> sh) & 0xffu;
+        qreg[0] = lane < k ? nlk_pl_decode(bc, px, py, r) : 0u;
+        greg[0] = lane < nagg ? nlk_pl_decode(bg, px, py, r) : 0u;
+      }
+    }
+    if (unpacked) {
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int i = lane + 64 * m;
-      qreg[m] = i < k ? topk[t * g.kmax + i] : 0u;
-      greg[m] = i < nagg ? gcoords[t * g.gstride + i] : 0u;
+      for (int m = 0; m < NR; ++m) {
+        const int i = lane + 64 * m;
+        qreg[m] = i < k ? topk[t * g.kmax + i] : 0u;
+        greg[m] = i < nagg ? gcoords[t * g.gstride + i] : 0u;
+      }
     }
     // (validity bits of the kept candidates come with the records of the match kernel)
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+    for (int m = 0; m < NR; ++m)
       vbits[m] = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)rec_vb[2 * m], tt) |
                  ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)rec_vb[2 * m + 1], tt) << 32);
     const int np0a = __popcll(vbits[0]);
-    const int np0 = np0a + __popcll(vbits[1]);
+    int np0 = np0a;
+    if constexpr (NR > 1) np0 += __popcll(vbits[1]);
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
+    for (int m = 0; m < NR; ++m) {
       const int rank = (m ? np0a : 0) + __popcll(vbits[m] & ((1ull << lane) - 1ull));
       gbits[m] = __ballot(((vbits[m] >> lane) & 1ull) && rank < g.ntagg);
     }
@@ -496,9 +549,9 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
     float part_sum = 0.f;
     // per lane: offset (floats) of candidate (lane + 64 m)'s patch inside an image plane,
     // bit 31 = "has a valid previous patch"
-    uint32_t oreg[2];
+    uint32_t oreg[NR];
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+    for (int m = 0; m < NR; ++m)
       oreg[m] = (uint32_t)(nlk_y(qreg[m]) * g.w + nlk_x(qreg[m])) | ((uint32_t)((vbits[m] >> lane) & 1ull) << 31);
     const uint32_t o_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)oreg[0]) & 0x7fffffffu;
     if constexpr (!SEPA) {
@@ -536,7 +589,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
       const uint32_t e_slot = slot_prev ? e_prev : e_img, e_dead = o_first + e_img;
       auto slot_off = [&](int bb) -> uint32_t {
         const int ci = CB * bb + slot_c, cl = min(ci, k - 1);
-        const uint32_t oc = nlk_bperm_u(cl < 64 ? oreg[0] : oreg[1], cl & 63);
+        const uint32_t oc = nlk_bperm_u(word_of(oreg, cl), cl & 63);
         const bool live = ci < k && (oc & live_need) == live_need;
         return live ? (oc & 0x7fffffffu) + e_slot : e_dead;
       };
@@ -591,7 +644,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
         }
         if (HP) {
           // bit j of the lane group's pair of candidates: group membership (filter) / valid previous patch (smoother)
-          const uint64_t mw = MODE == 1 ? (b < 8 ? gbits[0] : gbits[1]) : (b < 8 ? vbits[0] : vbits[1]);
+          const uint64_t mw = MODE == 1 ? word_of(gbits, 8 * b) : word_of(vbits, 8 * b);
           const uint32_t mbyte = (uint32_t)(mw >> (8 * (b & 7))) & 0xffu;
 #if NLK_G8_S5TRACK
           // (filter) The group members are the FIRST valid candidates of the sorted list: while every candidate of every
@@ -768,7 +821,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
       const uint32_t e_dead = o_first + e_img;
       auto slot_offs = [&](int bb, uint32_t& oi, uint32_t& op) {
         const int ci = 8 * bb + hp, cl = min(ci, k - 1);
-        const uint32_t oc = nlk_bperm_u(cl < 64 ? oreg[0] : oreg[1], cl & 63);
+        const uint32_t oc = nlk_bperm_u(word_of(oreg, cl), cl & 63);
         const bool in_k = ci < k, valid = (oc >> 31) != 0u;
         const uint32_t o = oc & 0x7fffffffu;
         const bool live_i = MODE == 1 ? (in_k && valid) : in_k;
@@ -919,7 +972,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
         }
         if constexpr (HP) {
           // the 8 candidates of the batch: valid previous patch / group membership, one bit per lane quad of a half
-          const uint64_t vw = b < 8 ? vbits[0] : vbits[1], gw = b < 8 ? gbits[0] : gbits[1];
+          const uint64_t vw = word_of(vbits, 8 * b), gw = word_of(gbits, 8 * b);
           const uint32_t vch = (uint32_t)(vw >> (8 * (b & 7))) & 0xffu, gch = (uint32_t)(gw >> (8 * (b & 7))) & 0xffu;
           if constexpr (MODE == 1) {
             const bool mixed = (vch & ~gch) != 0u;  // (wave-uniform) valid candidates that are not members
@@ -1043,11 +1096,13 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
     auto member_off = [&](int n0) -> uint32_t {   // (element offset inside an image: channel plane + patch)
       const int n = min(n0 + bmm, nagg - 1);
       uint32_t qm;
-      if constexpr (M5) {  // (a step of five may straddle the two list words, and a bpermute's operand is the SOURCE lane's)
-        const uint32_t q0 = nlk_bperm_u(greg[0], n & 63), q1 = nlk_bperm_u(greg[1], n & 63);
+      if constexpr (NR == 1) {
+        qm = nlk_bperm_u(greg[0], n & 63);
+      } else if constexpr (M5) {  // (a step of five may straddle the two list words, and a bpermute's operand is the SOURCE lane's)
+        const uint32_t q0 = nlk_bperm_u(greg[0], n & 63), q1 = nlk_bperm_u(greg[NR - 1], n & 63);
         qm = n < 64 ? q0 : q1;
       } else {
-        qm = nlk_bperm_u(n < 64 ? greg[0] : greg[1], n & 63);
+        qm = nlk_bperm_u(word_of(greg, n), n & 63);
       }
       return (uint32_t)bchc * (uint32_t)npix + (uint32_t)(nlk_y(qm) * g.w + nlk_x(qm));
     };
@@ -1068,10 +1123,10 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
     // the temporal radius - then aggregates in straight-line code. (Before, each member brought ~20 scalar
     // instructions and five branches with it: a sixth of the kernel's time, measured with the member loop
     // compiled out.)
-    uint32_t mbase[2];
-    uint64_t inside[2];
+    uint32_t mbase[NR];
+    uint64_t inside[NR];
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
+    for (int m = 0; m < NR; ++m) {
       const int lx = nlk_x(greg[m]) - rx0, ly = nlk_y(greg[m]) - ry0;
       const bool in = lx >= 0 && ly >= 0 && lx + PSZ <= rw && ly + PSZ <= rh;
       mbase[m] = (uint32_t)(ly * rwp + lx);
@@ -1198,8 +1253,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
         int tile_off[NPX];
 #pragma unroll
         for (int m = 0; m < NPX; ++m)   // (a step of five may straddle the two 64-entry words)
-          tile_off[m] = (n0 + m) < 64 ? __builtin_amdgcn_readlane((int)mbase[0], (n0 + m) & 63)
-                                      : __builtin_amdgcn_readlane((int)mbase[1], (n0 + m) & 63);
+          tile_off[m] = __builtin_amdgcn_readlane((int)word_of(mbase, n0 + m), (n0 + m) & 63);
 #pragma unroll
         for (int m = 0; m < NPX; ++m) {
           if (agg_on) {  // (CH = 3: every lane owns a plane)
@@ -1256,9 +1310,9 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
             const int n = n0 + 4 * t + jm;   // (wave-uniform) the member this round adds
             if (n >= nagg) continue;
             const bool act_img = spl == t, act_w = spl == ((t + 1) & 3);
-            const bool in = ((n < 64 ? inside[0] >> n : inside[1] >> (n - 64)) & 1ull) != 0;
-            const int toff = n < 64 ? __builtin_amdgcn_readlane((int)mbase[0], n) : __builtin_amdgcn_readlane((int)mbase[1], n - 64);
-            const uint32_t q = n < 64 ? __builtin_amdgcn_readlane(greg[0], n) : __builtin_amdgcn_readlane(greg[1], n - 64);
+            const bool in = ((word_of(inside, n) >> (n & 63)) & 1ull) != 0;
+            const int toff = __builtin_amdgcn_readlane((int)word_of(mbase, n), n & 63);
+            const uint32_t q = __builtin_amdgcn_readlane(word_of(greg, n), n & 63);
             if (act_img || act_w) {
               float px[4];
 #pragma unroll
@@ -1290,8 +1344,9 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
         continue;
       }
       // "inside the tile" bits of the step's members (a step of five may straddle the two 64-entry words)
-      uint64_t inb = n0 < 64 ? inside[0] >> n0 : inside[1] >> (n0 - 64);
-      if (NPX > 4 && n0 < 64 && n0 + NPX > 64) inb |= inside[1] << (64 - n0);
+      uint64_t inb = word_of(inside, n0) >> (n0 & 63);
+      if constexpr (NR > 1)
+        if (NPX > 4 && n0 < 64 && n0 + NPX > 64) inb |= inside[1] << (64 - n0);
       constexpr uint32_t in_all = (1u << NPX) - 1u;
       if (((uint32_t)inb & in_all) == in_all && n0 + NPX <= nagg) {
         agg_fast(n0, PX);
@@ -1300,8 +1355,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
 #pragma unroll
       for (int m = 0; m < NPX; ++m) {
         if (n0 + m >= nagg) break;
-        const uint32_t q = (n0 + m) < 64 ? __builtin_amdgcn_readlane(greg[0], n0 + m)
-                                         : __builtin_amdgcn_readlane(greg[1], n0 + m - 64);
+        const uint32_t q = __builtin_amdgcn_readlane(word_of(greg, n0 + m), (n0 + m) & 63);
         const int qx = nlk_x(q), qy = nlk_y(q);
         float px[4] = {PX[m][0], PX[m][1], PX[m][2], PX[m][3]};
         const int lx = qx - rx0, ly = qy - ry0;

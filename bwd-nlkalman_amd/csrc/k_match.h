@@ -44,6 +44,7 @@ struct NlkTile {
   int block;          // 4 x 2-target blocks share their squared differences (0: NLK_MATCH_NOBLOCK, target by target)
   int threads;        // k_bm_topk: threads per workgroup (256, or 512 for tiles of 8 x 8 targets)
   int order;          // summation order of the distances: 0 = the reference's (exact), 1 = block-summed (opt-in; 8 x 8 patches)
+  int packed;         // != 0: the targets' packed lists (nlk_common.h) are written and flagged
 };
 
 // OR over the 64 lanes, in every lane. (Round 6: four DPP steps inside the rows of 16 lanes and the two row-swap
@@ -426,9 +427,8 @@ __device__ __forceinline__ void nlk_match_epilogue(const NlkGeom& g, size_t t, i
                                           const uint8_t* __restrict__ vmap,
                                           uint32_t* __restrict__ topk, NlkTarget* __restrict__ tinfo,
                                           uint32_t* __restrict__ gcoords,
-                                          uint64_t* __restrict__ marks, int lane) {
+                                          uint64_t* __restrict__ marks, bool plists, int lane) {
   const int step = STEP ? STEP : g.step;
-  NlkTarget info = {0, 0, 0, prev_p, {0ull, 0ull}};
   // --- group membership: the first ntagg kept candidates that have a valid
   // previous patch, or (none valid) the first ntagg kept candidates
   int np0 = 0;
@@ -477,14 +477,26 @@ __device__ __forceinline__ void nlk_match_epilogue(const NlkGeom& g, size_t t, i
     if (lane == 0) gcoords[t * g.gstride] = nlk_pack_xy(px, py);
   }
   mbits = nlk_wave_or(mbits);
+  // --- packed lists (nlk_common.h; plists false: the call keeps none). A member list is never longer than the
+  // candidate list, so k decides; every entry lies in the target's window of radius r <= 7 and therefore encodes. (The
+  // smoother's pass-through target, whose member is the target itself, keeps the flag clear.)
+  const int pl_r = nlk_target_radius(g, prev_p);
+  const bool packed = plists && nlk_pl_target_fits(k, pl_r, g.smoother && np0 == 0);  // (wave-uniform)
   if (lane == 0) {
-    info.nsel = k;
-    info.np0 = np0;
-    info.nagg = nagg;
-    info.flags = prev_p | (mark << 1);
-    info.vbits[0] = vb[0]; info.vbits[1] = vb[1];
-    tinfo[t] = info;
+    nlk_target_store(tinfo + t, k, np0, nagg, prev_p | (mark << 1) | (packed ? NLK_TF_PACKED : 0), vb[0], vb[1]);
     marks[t] = mbits;
+  }
+  if (packed) {
+    // Written LAST, from the lists in LDS, every lane the byte of entry `lane`: at this point nothing of the epilogue
+    // is live any more (carried through it, or stored from its loops, the two bytes cost the 64-register matchers
+    // spills in their row loops: C2 match + 0.013 ms). The byte code: nlk_common.h.
+    uint8_t* const rec = reinterpret_cast<uint8_t*>(tinfo[t].pl);
+    if (lane < k) {
+      rec[lane] = (uint8_t)nlk_pl_byte(nlk_pl_word(sel[lane], px, py, pl_r));
+    }
+    if (lane < nagg) {
+      rec[NLK_PL_MAX + lane] = (uint8_t)nlk_pl_byte(nlk_pl_word(np0 ? grp[lane] : sel[lane], px, py, pl_r));
+    }
   }
 }
 
@@ -595,7 +607,7 @@ k_bm_topk(const float* __restrict__ img, const uint8_t* __restrict__ vmap, NlkGe
         info.nagg = 1;
         if (lane == 0) gcoords[t * g.gstride] = nlk_pack_xy(px, py);
       }
-      if (lane == 0) { tinfo[t] = info; marks[t] = 0; }
+      if (lane == 0) { nlk_target_store(tinfo + t, info.nsel, info.np0, info.nagg, info.flags, 0ull, 0ull); marks[t] = 0; }
       return;
     }
     const int wsz = (g.smoother || prev_p) ? g.wsz_t : g.wsz_x;
@@ -627,7 +639,7 @@ k_bm_topk(const float* __restrict__ img, const uint8_t* __restrict__ vmap, NlkGe
       if (lane == 0) wide_list[atomicAdd(wide_count, 1u)] = (uint32_t)t;
       return;
     }
-    nlk_match_epilogue<PSZ / 2>(g, t, px, py, prev_p, k, sel, grp, vmap, topk, tinfo, gcoords, marks, lane);
+    nlk_match_epilogue<PSZ / 2>(g, t, px, py, prev_p, k, sel, grp, vmap, topk, tinfo, gcoords, marks, tl.packed != 0, lane);
     __builtin_amdgcn_wave_barrier();
   };
 
@@ -701,7 +713,7 @@ k_bm_topk(const float* __restrict__ img, const uint8_t* __restrict__ vmap, NlkGe
         const int prev_p = __builtin_amdgcn_readlane(rec_prev, ty * cx + tx);
         const int k = min(prev_p ? g.npt : g.npx, n);
         nlk_match_select<PSZ, CH, M>(a2, wxy, n, k, px - wsz, py - wsz, surv, sel, lane);
-        nlk_match_epilogue<PSZ / 2>(g, t, px, py, prev_p, k, sel, grp, vmap, topk, tinfo, gcoords, marks, lane);
+        nlk_match_epilogue<PSZ / 2>(g, t, px, py, prev_p, k, sel, grp, vmap, topk, tinfo, gcoords, marks, tl.packed != 0, lane);
         __builtin_amdgcn_wave_barrier();
       }
     };
@@ -772,7 +784,7 @@ k_bm_wide(const float* __restrict__ img, const uint8_t* __restrict__ vmap, NlkGe
     else
       nlk_match_target<PSZ, CH, MAXM, ORD>(tile, plane, rwp, tl_tgt, plane, rwp, 0, nwx, n, k, x0, y0,
                                            surv, sel, lane);
-    nlk_match_epilogue<PSZ / 2>(g, t, px, py, prev_p, k, sel, grp, vmap, topk, tinfo, gcoords, marks, lane);
+    nlk_match_epilogue<PSZ / 2>(g, t, px, py, prev_p, k, sel, grp, vmap, topk, tinfo, gcoords, marks, tl.packed != 0, lane);
     __builtin_amdgcn_wave_barrier();
   }
 }

@@ -32,7 +32,7 @@ k_bm_generic(const float* __restrict__ img, const uint8_t* __restrict__ vmap, Nl
       info.nagg = 1;
       if (lane == 0) gcoords[t * g.gstride] = nlk_pack_xy(px, py);
     }
-    if (lane == 0) { tinfo[t] = info; marks[t] = 0; }
+    if (lane == 0) { nlk_target_store(tinfo + t, info.nsel, info.np0, info.nagg, info.flags, 0ull, 0ull); marks[t] = 0; }
     return;
   }
   const int wsz = (g.smoother || prev_p) ? g.wsz_t : g.wsz_x;
@@ -105,5 +105,5 @@ k_bm_generic(const float* __restrict__ img, const uint8_t* __restrict__ vmap, Nl
     }
   }
   nlk_wave_lds_fence();
-  nlk_match_epilogue(g, t, px, py, prev_p, k, sel, grp, vmap, topk, tinfo, gcoords, marks, lane);
+  nlk_match_epilogue(g, t, px, py, prev_p, k, sel, grp, vmap, topk, tinfo, gcoords, marks, false, lane);
 }

@@ -18,8 +18,10 @@ int launch_match_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const NlkT
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // k_bm_wide: the queue length is only known on the device, so a fixed grid strides over it
   const int grid = wide ? 512 : nlk_xcd_grid(tl.ntx * tl.nty);
+  NlkTile tk = tl;
+  tk.packed = v.packed;  // (the call keeps packed lists in the target records: nlk_common.h)
   hipLaunchKernelGGL(kern, dim3(grid), dim3(wide ? NLK_BM_THREADS : tl.threads), lds, v.stream, img,
-                     (const uint8_t*)c->vmap.p, g, tl, v.topk, v.tinfo, v.gcoords, v.marks, v.wide + 1, v.wide);
+                     (const uint8_t*)c->vmap.p, g, tk, v.topk, v.tinfo, v.gcoords, v.marks, v.wide + 1, v.wide);
   HIPCHK(c, hipGetLastError());
   return NLK_OK;
 }

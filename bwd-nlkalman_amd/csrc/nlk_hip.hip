@@ -80,6 +80,7 @@ int launch_group(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float*
   // instantiated (nlk_fixed_shape) and its run-time shape (patch size and channel count from NlkGeom) otherwise, as
   // patches above 16 do
   const bool lists_fit = g.kmax <= 128 && g.gstride <= 128;
+  c->group_packed = 0;
   memset(c->group_shape, 0, sizeof c->group_shape);  // (nlk_ctx_last_group_shape: "another launcher ran", until tu_group8.hip says otherwise)
   if (g.psz > 16) return nlk_launch_group_any(c, v, g, img, cur, prev, acc, active);  // (GroupAny: 17..32)
   if (nlk_set(c->sw.generic_group) || !lists_fit)
@@ -279,6 +280,11 @@ int nlk_ctx_last_group_shape(nlk_ctx* c, int out[12]) {
   return NLK_OK;
 }
 
+int nlk_ctx_last_group_packed(nlk_ctx* c) {
+  if (!c) return fail(nullptr, NLK_EINVAL, "null context");  // (negative)
+  return c->group_packed;
+}
+
 int nlk_ctx_set_stream(nlk_ctx* c, void* s) {
   if (!c) return NLK_EINVAL;
   c->stream = (hipStream_t)s;  // NULL is the legacy default stream (what torch uses by default)
@@ -425,6 +431,7 @@ static NlkRecView view_rows(nlk_ctx* c, const NlkGeom& g, hipStream_t stream, in
   v.topk = (uint32_t*)c->topk.p + t0 * g.kmax;
   v.tinfo = (NlkTarget*)c->tinfo.p + t0;
   v.gcoords = (uint32_t*)c->gcoords.p + t0 * g.gstride;
+  v.packed = c->last.packed;
   v.marks = (marks_ext ? marks_ext : (uint64_t*)c->marks.p) + t0;
   v.wide = (uint32_t*)c->wide.p + t0 + band;  // (every band: its own counter in front of its own list)
   return v;
@@ -624,7 +631,11 @@ static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* pr
     if (pl.lds_w > 160 * 1024) { pl.generic = true; pl.wide = false; }
     pl.maxm_w = (ncand + 63) / 64;
   }
-  c->last = {g, pl.img_match, pl.img_cur, pl.img_prev, pl.img_diff, true};
+  // Packed lists (nlk_common.h): kept by the tiled matchers wherever k_group8m's packed instantiation could read them
+  // (nlk_packed_geom; the matcher flags the targets whose record is valid, tu_group8.hip decides per launch).
+  // NLK_PACKED_LISTS=0: none kept, the 32-bit lists only.
+  const bool packed = !pl.generic && nlk_or(c->sw.packed_lists, 1) != 0 && nlk_packed_geom(g);
+  c->last = {g, pl.img_match, pl.img_cur, pl.img_prev, pl.img_diff, true, packed};
   return NLK_OK;
 }
 
@@ -1162,6 +1173,48 @@ int nlk_host_tables(int psz, float* basis, float* window, float* basis12_regs) {
       nlk_host12::nlk_dct12_fast_fwd(e);
       for (int k = 0; k < 12; ++k) basis12_regs[k * 12 + j] = e[k];
     }
+  return NLK_OK;
+}
+
+// The packed-list byte code for tests without a device, through the functions the kernels call (nlk_common.h): an
+// entry at displacement (dx, dy) from a target at (px, py) that searched radius r and kept k candidates, `passthrough`
+// as in nlk_pl_target_fits. *byte = its code (nlk_pl_word, nlk_pl_byte: the matcher's epilogue), back[0..1] = the frame
+// coordinate decoded from it again (nlk_pl_decode: k_group8m); either may be null. NLK_EINVAL where the target cannot
+// have a valid record (nlk_pl_target_fits: what the epilogue asks before it sets the flag) or the entry has no code.
+int nlk_host_packed_entry(int px, int py, int dx, int dy, int r, int k, int passthrough, unsigned int* byte, int* back) {
+  if (px < 0 || py < 0 || px + dx < 0 || py + dy < 0 || px + dx > 65535 || py + dy > 65535)
+    return fail(nullptr, NLK_EINVAL, "entry (%d + %d, %d + %d) outside a frame", px, dx, py, dy);
+  if (!nlk_pl_target_fits(k, r, passthrough != 0))
+    return fail(nullptr, NLK_EINVAL, "no packed record for a target with %d candidates at radius %d%s", k, r,
+                passthrough ? " (pass-through)" : "");
+  const uint32_t word = nlk_pl_word(nlk_pack_xy(px + dx, py + dy), px, py, r);
+  if (!nlk_pl_encodes(word, r))
+    return fail(nullptr, NLK_EINVAL, "displacement (%d, %d) at radius %d has no packed code", dx, dy, r);
+  const uint32_t b = nlk_pl_byte(word);
+  if (byte) *byte = b;
+  if (back) {
+    const uint32_t q = nlk_pl_decode(b, px, py, r);
+    back[0] = nlk_x(q);
+    back[1] = nlk_y(q);
+  }
+  return NLK_OK;
+}
+
+// How many targets of the last match phase carry a valid packed record (NLK_TF_PACKED): tests only
+int nlk_ctx_count_packed(nlk_ctx* c, int* count) {
+  if (!c || !count || !c->last.valid) return fail(c, NLK_EINVAL, "no frame has been processed");
+  NLK_USE_DEVICE(c);
+  const int n = c->last.g.ngx * c->last.g.ngy;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  NlkTarget* t = (NlkTarget*)malloc(sizeof(NlkTarget) * n);
+  if (!t) return fail(c, NLK_ENOMEM, "host malloc failed");
+  const hipError_t e = hipMemcpy(t, c->tinfo.p, sizeof(NlkTarget) * n, hipMemcpyDeviceToHost);
+  int m = 0;
+  if (e == hipSuccess)
+    for (int i = 0; i < n; ++i) m += (t[i].flags & NLK_TF_PACKED) ? 1 : 0;
+  free(t);
+  HIPCHK(c, e);
+  *count = m;
   return NLK_OK;
 }
 

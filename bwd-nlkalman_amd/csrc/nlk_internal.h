@@ -38,6 +38,7 @@ struct NlkRecView {
   uint32_t* topk = nullptr;      // [targets][kmax]
   NlkTarget* tinfo = nullptr;    // [targets]
   uint32_t* gcoords = nullptr;   // [targets][gstride]
+  bool packed = false;           // the match phase keeps packed lists in the target records (nlk_common.h)
   uint64_t* marks = nullptr;     // [targets]
   uint32_t* wide = nullptr;      // [0] = queue length, then the queued targets (k_bm_wide)
   NlkChase chase;                // words != nullptr: the group kernel is to replay the processed mask itself
@@ -55,7 +56,7 @@ struct NlkRecView {
   X(match_noblock, "NLK_MATCH_NOBLOCK") X(match_order, "NLK_MATCH_ORDER") X(commit_wave, "NLK_COMMIT_WAVE") X(commit_lds, "NLK_COMMIT_LDS")    \
   X(commit_band, "NLK_COMMIT_BAND") X(no_chase, "NLK_NO_CHASE") X(chase_test_skip0, "NLK_CHASE_TEST_SKIP0") X(bands, "NLK_BANDS") X(host_bands, "NLK_HOST_BANDS")                    \
   X(host_trace, "NLK_HOST_TRACE") X(gtx, "NLK_GTX") X(gty, "NLK_GTY") X(g8_tail, "NLK_G8_TAIL")              \
-  X(g8_single, "NLK_G8_SINGLE") X(tv_wg_pixels, "NLK_TV_WG_PIXELS") X(tv_unblocked, "NLK_TV_UNBLOCKED")      \
+  X(g8_single, "NLK_G8_SINGLE") X(packed_lists, "NLK_PACKED_LISTS") X(tv_wg_pixels, "NLK_TV_WG_PIXELS") X(tv_unblocked, "NLK_TV_UNBLOCKED")      \
   X(tv_batch, "NLK_TV_BATCH") X(tv_mid, "NLK_TV_MID") X(tv_shape, "NLK_TV_SHAPE") X(tv_deep, "NLK_TV_DEEP")  \
   X(tv_inline, "NLK_TV_INLINE") X(tv_wg_full, "NLK_TV_WG_FULL") X(tv_look, "NLK_TV_LOOK") X(tv_look2, "NLK_TV_LOOK2") X(tv_trace, "NLK_TV_TRACE")
 struct NlkSwitches {
@@ -118,7 +119,9 @@ struct nlk_ctx {
     NlkGeom g;
     const float *match, *cur, *prev, *diff;
     bool valid;
+    bool packed;  // the match phase keeps packed lists (nlk_common.h) in the target records
   } last{};
+  int group_packed = 0;      // nlk_ctx_last_group_packed: the last group launch read its lists packed
   int group_shape[12] = {};  // nlk_ctx_last_group_shape: written after a group launch is enqueued, read by nothing else
   // profiling: one set of NEV events per frame call, read back (and averaged)
   // only by nlk_ctx_get_timings, so the timed loop never synchronises
@@ -193,6 +196,17 @@ static inline bool nlk_active_is_lazy(const nlk_ctx* c) { return c->lazy_ngx != 
 // the shapes the tiled matchers (k_match.h) and the LDS-DCT group kernel (k_group_lds.h) are instantiated for
 static inline bool nlk_fixed_shape(int psz, int ch) {
   return (psz == 4 || psz == 6 || psz == 8 || psz == 10 || psz == 12 || psz == 16) && (ch == 1 || ch == 3);
+}
+
+// Packed lists (nlk_common.h): can the targets of a call of this geometry have them, and k_group8m's packed-list
+// instantiation run it? 8 x 8 patches, the filter; the lists of the call's DOMINANT kind of target - in a temporal
+// frame the targets with a valid previous patch - fit a record and its radius has a byte code. The other kind (a
+// temporal frame's spatial-branch targets: npatches_x candidates, the spatial radius) is told apart target by target
+// (NLK_TF_PACKED) and read as 32-bit lists by the same kernel, which keeps ONE round of 64 entries per list.
+static inline bool nlk_packed_geom(const NlkGeom& g) {
+  const bool t = g.smoother || g.have_prev;
+  return g.psz == 8 && (g.ch == 1 || g.ch == 3) && !g.smoother && (t ? g.npt : g.npx) <= NLK_PL_MAX &&
+         g.gstride <= NLK_PL_MAX && g.kmax <= 64 && (t ? g.wsz_t : g.wsz_x) <= NLK_PL_RMAX;
 }
 
 // ---- launchers (one translation unit each): every one enqueues on the view's stream and works on the view's

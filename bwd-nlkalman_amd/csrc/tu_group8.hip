@@ -5,7 +5,7 @@
 #include "k_group8m.h"
 #include "nlk_internal.h"
 
-const void* nlk_group8m_ilp_kernel(int ch, bool smoother, int sep);  // tu_group8_ilp.hip
+const void* nlk_group8m_ilp_kernel(int ch, bool smoother, int sep, bool packed);  // tu_group8_ilp.hip
 
 namespace {
 
@@ -153,6 +153,15 @@ int launch_group8_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const flo
   };
   const int npass = split ? 2 : 1;
   NlkGTile tls[2] = {shape(0), shape(split ? 1 : 0)};
+  // The packed-list instantiation (k_group8m.h; the filter's kernels only), per launch: the match phase kept packed
+  // lists for these rows (nlk_hip.hip: plan_frame - a tiled matcher, NLK_PACKED_LISTS not 0), the lists of the call's
+  // dominant targets fit a record (nlk_packed_geom), the radius of the LDS window has a byte code, and the tile's
+  // records fit the two registers that hold them
+  bool packed[2] = {false, false};
+  for (int pass = 0; pass < npass; ++pass)
+    packed[pass] = mfma && !SMO && v.packed && nlk_packed_geom(g) &&
+                   tls[pass].wmax <= NLK_PL_RMAX && tls[pass].tgx * tls[pass].tgy <= 8 &&
+                   !(CH == 1 && sep == 2);  // (one channel in the hybrid form - NLK_GROUP_SEP=2, no default - spills already)
   // (a tile's target records sit one per lane of its wavefront, and both kernels read them back by lane number; the
   // LDS limit below would let a 65 x 1 tile through)
   for (int pass = 0; pass < npass; ++pass)
@@ -194,10 +203,13 @@ int launch_group8_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const flo
                  const uint32_t*, const NlkTarget*, const uint32_t*, const uint8_t*, const float*,
                  const float*, float*);
     kern = !mfma ? k_group8<CH, SMO> : sep == 0 ? k_group8m<CH, SMO, 0> : sep == 2 ? k_group8m<CH, SMO, 2> : k_group8m<CH, SMO, 6>;
+    if constexpr (!SMO)
+      if (packed[pass])
+        kern = sep == 0 ? k_group8m<CH, false, 0, 0, true> : (sep == 2 && CH == 3) ? k_group8m<3, false, 2, 0, true> : k_group8m<CH, false, 6, 0, true>;
     // (the same kernel compiled under the max-ilp scheduler, where that is the faster one: tu_group8_ilp.hip;
     // NLK_GROUP_ILP=0 keeps this unit's)
     if (mfma && nlk_or(c->sw.group_ilp, 1) != 0)
-      if (const void* k2 = nlk_group8m_ilp_kernel(CH, SMO, sep)) kern = reinterpret_cast<decltype(kern)>(const_cast<void*>(k2));
+      if (const void* k2 = nlk_group8m_ilp_kernel(CH, SMO, sep, packed[pass])) kern = reinterpret_cast<decltype(kern)>(const_cast<void*>(k2));
     HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds));
     const float* basis = (const float*)c->tabs.p;
@@ -214,6 +226,7 @@ int launch_group8_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const flo
   const int report[12] = {mfma ? NLK_GROUP_FAMILY_8M : NLK_GROUP_FAMILY_8, sep, t0.tgx, t0.tgy, t0.ntx, t0.nty,
                           t0.nty_full, t0.single, npass, t0.chase, split ? tls[1].tgx : 0, split ? tls[1].tgy : 0};
   memcpy(c->group_shape, report, sizeof report);
+  c->group_packed = (packed[0] ? 1 : 0) | (npass > 1 && packed[1] ? 2 : 0);
   return NLK_OK;
 }
 

@@ -9,8 +9,9 @@
 #include "nlk_internal.h"
 
 // the kernel for (channels, smoother, DCT form) if this unit holds it, else nullptr
-const void* nlk_group8m_ilp_kernel(int ch, bool smoother, int sep) {
-  if (ch == 3 && !smoother && sep == 2) return (const void*)k_group8m<3, false, 2, 1>;
-  if (ch == 3 && !smoother && sep == 6) return (const void*)k_group8m<3, false, 6, 1>;
+// (`packed`: the packed-list instantiation, k_group8m.h)
+const void* nlk_group8m_ilp_kernel(int ch, bool smoother, int sep, bool packed) {
+  if (ch == 3 && !smoother && sep == 2) return packed ? (const void*)k_group8m<3, false, 2, 1, true> : (const void*)k_group8m<3, false, 2, 1>;
+  if (ch == 3 && !smoother && sep == 6) return packed ? (const void*)k_group8m<3, false, 6, 1, true> : (const void*)k_group8m<3, false, 6, 1>;
   return nullptr;
 }

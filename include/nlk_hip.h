@@ -108,6 +108,10 @@ int nlk_ctx_reload_switches(nlk_ctx *ctx);
  *   out[10..11]  far pass: tgx, tgy (0 when there is none) */
 enum { NLK_GROUP_FAMILY_OTHER = 0, NLK_GROUP_FAMILY_8M = 1, NLK_GROUP_FAMILY_8 = 2 };
 int nlk_ctx_last_group_shape(nlk_ctx *ctx, int out[12]);
+/* ... and whether that launch was k_group8m's packed-list instantiation, which reads a tile's candidate and member
+ * lists as one word per lane (csrc/nlk_common.h; NLK_PACKED_LISTS=0 keeps the 32-bit lists): bit 0 = pass 0,
+ * bit 1 = the far pass of deterministic mode; 0 after any other launcher; negative for a null context. */
+int nlk_ctx_last_group_packed(nlk_ctx *ctx);
 /* run the context's work on an externally owned hipStream_t; NULL is the legacy
  * default stream itself (what torch.cuda.current_stream() is unless changed), so
  * that the kernels order with the caller's own work on that stream.
@@ -618,6 +622,15 @@ int nlk_strips_stats(nlk_strips *s, float phase_ms[7], float *issue_us, int *gra
  * 12-point flow graph of the packed-lane kernel applies (csrc/k_dct12.h, evaluated on the host: column j =
  * graph(e_j)). Any pointer may be NULL. */
 int nlk_host_tables(int psz, float *basis, float *window, float *basis12_regs);
+/* the byte code of the packed candidate / member lists (csrc/nlk_common.h), on the host through the very functions
+ * the kernels call (tests only; no device needed): an entry at displacement (dx, dy) from a target at (px, py) that
+ * searched radius r and kept k candidates (passthrough: the smoother's target without a valid previous patch).
+ * *byte = its code as the matcher stores it, back[0..1] = the frame coordinate (x, y) the group kernel decodes from
+ * that byte; either may be NULL. NLK_EINVAL where the target cannot have a valid record (more than 32 candidates, r
+ * above 7, pass-through) or the displacement lies outside the radius. */
+int nlk_host_packed_entry(int px, int py, int dx, int dy, int r, int k, int passthrough, unsigned int *byte, int *back);
+/* how many targets of the context's last match phase carry a valid packed record (tests only; synchronises) */
+int nlk_ctx_count_packed(nlk_ctx *ctx, int *count);
 
 #ifdef __cplusplus
 }
