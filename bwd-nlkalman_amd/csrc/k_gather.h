@@ -7,7 +7,7 @@
 // every pixel, the slabs of the tiles that cover it in ascending tile order: one thread per pixel,
 // no atomics, the same sum order every time.
 #pragma once
-#include "k_group8.h"  // NlkGTile
+#include "k_group_tile.h"  // NlkGTile
 #include "nlk_common.h"
 
 // `tcount[0]` = number of flagged tiles of the launch, `tcount[1 + ty]` = of tile row ty (added by the

@@ -5,15 +5,30 @@
 // basis in both directions: with F_q[i][j] = X[i][j] +- X[i][7-j] +- X[7-i][j]
 // +- X[7-i][7-j] (q = parity of the vertical / horizontal frequency, i, j < 4)
 //   Y[2a+qr][2b+qc] = sum_{i,j} C[2a+qr][i] C[2b+qc][j] F_q[i][j]
-// It runs in two forms, chosen per pass by the template argument SEP (tu_group8.hip picks by mode):
+// It runs in two forms, chosen per pass by the template argument SEP (bit 1: pass B, bit 2: pass A):
 //   Kronecker  four 16x16 matrices D_q applied to four 16-vectors: 1024 MACs per patch, all of them
 //              useful, as v_mfma_f32_16x16x4_f32 products over 16 patches at a time (exact f32: the
 //              f32 MFMA is an fmaf chain); the inverse uses the same matrices. Candidates land in
-//              REGISTERS: what the statistics of pass A want. Roles below.
+//              REGISTERS. Roles below.
 //   separable  Y_q = C_qr F_q C_qc^T, 512 MACs per patch, on v_mfma_f32_4x4x1_16B_f32 with one patch
-//              per lane quad (round 5; described where its helpers are defined): what pass B runs
-//              for the first iteration's groups; a separable pass A exists (SEP bit 2) and loses.
-// Both unfold with the same butterflies.
+//              per lane quad in pass B and half a patch per quad in pass A (described where the
+//              helpers and that pass A are defined).
+// Both unfold with the same butterflies. Which form runs where is the launcher's choice (tu_group8.hip,
+// sep_default): SEP = 6, separable in both passes, for one-channel frames and for the RGB filter's temporal
+// frames; SEP = 2, Kronecker statistics and separable pass B, for RGB first frames and the RGB smoother;
+// SEP = 0, Kronecker in both, for those RGB calls when their groups hold fewer than four members. NLK_GROUP_SEP
+// overrides.
+//
+// The kernel is one function; its parts, in the order they run, and what each leaves for the next:
+//   mask replay        (chase_replay; workgroup 0, or any workgroup rescuing itself) the tagged decision words
+//   tile               tile_x/y/id, first target gx0/gy0, targets cx x cy, frame region rx0/ry0/rw/rh
+//   tile records       one target per lane: rec_act, rec_nsel, rec_nagg, rec_vb[], (PK) pk_c / pk_g
+//   lane constants     lane roles, the basis operands dA/dI or sE/sG/Er, poff[], win[], element and row offsets
+//   per target         lists: k, nagg, np0, in0/in1/ing, passthrough, qreg/greg/oreg, vbits/gbits, o_first
+//                      pass A (pass_a; Kronecker, or separable with sep_gain): gains and means in the stash, part_sum
+//                      pass B (member_off, step_px, agg_fast, the G16 rounds, the path outside the tile): the tile
+//   flush              the tile to the frame's accumulator with atomics, or to the tile's slab
+// (profiles/group8m_split.txt: what became of turning these parts into functions.)
 //
 // Lane roles of the Kronecker form (lo = lane & 15, g4 = lane >> 4):
 //   loads    lane = patch slot lo, rows g4 and 7-g4 of that patch (2 x 8 floats);
@@ -36,7 +51,7 @@
 #pragma once
 #include "nlk_common.h"
 #include "k_commit_rows.h"
-#include "k_group8.h"
+#include "k_group_tile.h"
 #include "k_group_math.h"
 #include <type_traits>
 
@@ -62,6 +77,13 @@ __device__ __forceinline__ float nlk_bperm(float v, int src_lane) {
 }
 __device__ __forceinline__ uint32_t nlk_bperm_u(uint32_t v, int src_lane) {
   return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
+}
+
+// entry i (wave-uniform) of a pair of 64-entry words / its word
+template <typename T, int N>
+__device__ __forceinline__ T nlk_word_of(const T (&a)[N], int i) {
+  if constexpr (N > 1) return i < 64 ? a[0] : a[1];
+  else return a[0];
 }
 
 // rows g4 and 7-g4 of the 8x8 patch at p (row stride w). Always executed: slots without
@@ -481,11 +503,6 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
     // group-membership bits of the candidates as wave-uniform masks
     uint32_t qreg[NR], greg[NR];
     uint64_t vbits[NR], gbits[NR];
-    // entry i (wave-uniform) of a pair of 64-entry words / its word
-    auto word_of = [&](const auto& a, int i) {
-      if constexpr (NR > 1) return i < 64 ? a[0] : a[1];
-      else return a[0];
-    };
     bool unpacked = true;
     if constexpr (PK) {
       const int fl = rec_tt >> 16;
@@ -589,7 +606,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
       const uint32_t e_slot = slot_prev ? e_prev : e_img, e_dead = o_first + e_img;
       auto slot_off = [&](int bb) -> uint32_t {
         const int ci = CB * bb + slot_c, cl = min(ci, k - 1);
-        const uint32_t oc = nlk_bperm_u(word_of(oreg, cl), cl & 63);
+        const uint32_t oc = nlk_bperm_u(nlk_word_of(oreg, cl), cl & 63);
         const bool live = ci < k && (oc & live_need) == live_need;
         return live ? (oc & 0x7fffffffu) + e_slot : e_dead;
       };
@@ -644,7 +661,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
         }
         if (HP) {
           // bit j of the lane group's pair of candidates: group membership (filter) / valid previous patch (smoother)
-          const uint64_t mw = MODE == 1 ? word_of(gbits, 8 * b) : word_of(vbits, 8 * b);
+          const uint64_t mw = MODE == 1 ? nlk_word_of(gbits, 8 * b) : nlk_word_of(vbits, 8 * b);
           const uint32_t mbyte = (uint32_t)(mw >> (8 * (b & 7))) & 0xffu;
 #if NLK_G8_S5TRACK
           // (filter) The group members are the FIRST valid candidates of the sorted list: while every candidate of every
@@ -821,7 +838,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
       const uint32_t e_dead = o_first + e_img;
       auto slot_offs = [&](int bb, uint32_t& oi, uint32_t& op) {
         const int ci = 8 * bb + hp, cl = min(ci, k - 1);
-        const uint32_t oc = nlk_bperm_u(word_of(oreg, cl), cl & 63);
+        const uint32_t oc = nlk_bperm_u(nlk_word_of(oreg, cl), cl & 63);
         const bool in_k = ci < k, valid = (oc >> 31) != 0u;
         const uint32_t o = oc & 0x7fffffffu;
         const bool live_i = MODE == 1 ? (in_k && valid) : in_k;
@@ -832,15 +849,6 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
       auto row_read = [&](uint32_t off, int cc, float (&R)[8]) {
 #ifdef NLK_G8_EXP_NOROWS   // (timing experiment: only the first batch's rows are loaded)
         if (rows_seen >= 2) { asm volatile("" : "+v"(R[0]), "+v"(R[3]), "+v"(R[5]), "+v"(R[7]) : "v"(off)); return; }
-        ++rows_seen;
-#endif
-#ifdef NLK_G8_EXP_LDSROWS   // (timing experiment: the rows read from LDS - garbage from the tile - as a staged window would give them)
-        if (rows_seen >= 2) {
-          const float* wp = smem + ((off + (uint32_t)cc * 7u + (uint32_t)(lane & 7) * 18u) % 1500u);
-#pragma unroll
-          for (int c = 0; c < 8; ++c) R[c] = wp[c];
-          return;
-        }
         ++rows_seen;
 #endif
         // lanes 2 m and 2 m + 1 own rows 2 m and 2 m + 1 of their candidate; each of the two loads takes ONE of those
@@ -917,26 +925,6 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
       for (int b = 0; b < nb; ++b) {
         const bool wrap = b + 1 == nb;
         const int chn = wrap ? min(ch + 1, CH - 1) : ch;
-#ifdef NLK_G8_EXP_LDSROWS   // (timing experiment: the cost of staging two 18 x 18 windows per channel)
-        if (HP && b == 0) {
-          float* win = stash + nlk_g8_stash_floats<CH, SEP>();
-          const uint32_t back = 10u * (uint32_t)g.w + 10u;
-          const uint32_t wo = (o_first > back ? o_first - back : o_first) + (uint32_t)ch * (uint32_t)npix;
-          float tmp[12];
-#pragma unroll
-          for (int kq = 0; kq < 6; ++kq) {
-            const uint32_t idx = min((uint32_t)lane + 64u * kq, 323u), r = (idx * 3641u) >> 16, cx = idx - 18u * r;
-            tmp[kq] = pbase[(size_t)(e_img + wo + r * (uint32_t)g.w + cx)];
-            tmp[6 + kq] = pbase[(size_t)(e_prev + wo + r * (uint32_t)g.w + cx)];
-          }
-#pragma unroll
-          for (int kq = 0; kq < 6; ++kq) {
-            win[(lane + 64 * kq) % (NLK_G8_LDS_PAD / 8)] = tmp[kq];
-            win[NLK_G8_LDS_PAD / 8 + (lane + 64 * kq) % (NLK_G8_LDS_PAD / 8)] = tmp[6 + kq];
-          }
-          nlk_wave_lds_order();
-        }
-#endif
         float Fi[2][4], Fp[2][4];
         fold_half(Ri, Fi);
         if (HP) fold_half(Rp, Fp);
@@ -972,7 +960,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
         }
         if constexpr (HP) {
           // the 8 candidates of the batch: valid previous patch / group membership, one bit per lane quad of a half
-          const uint64_t vw = word_of(vbits, 8 * b), gw = word_of(gbits, 8 * b);
+          const uint64_t vw = nlk_word_of(vbits, 8 * b), gw = nlk_word_of(gbits, 8 * b);
           const uint32_t vch = (uint32_t)(vw >> (8 * (b & 7))) & 0xffu, gch = (uint32_t)(gw >> (8 * (b & 7))) & 0xffu;
           if constexpr (MODE == 1) {
             const bool mixed = (vch & ~gch) != 0u;  // (wave-uniform) valid candidates that are not members
@@ -1102,7 +1090,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
         const uint32_t q0 = nlk_bperm_u(greg[0], n & 63), q1 = nlk_bperm_u(greg[NR - 1], n & 63);
         qm = n < 64 ? q0 : q1;
       } else {
-        qm = nlk_bperm_u(word_of(greg, n), n & 63);
+        qm = nlk_bperm_u(nlk_word_of(greg, n), n & 63);
       }
       return (uint32_t)bchc * (uint32_t)npix + (uint32_t)(nlk_y(qm) * g.w + nlk_x(qm));
     };
@@ -1253,7 +1241,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
         int tile_off[NPX];
 #pragma unroll
         for (int m = 0; m < NPX; ++m)   // (a step of five may straddle the two 64-entry words)
-          tile_off[m] = __builtin_amdgcn_readlane((int)word_of(mbase, n0 + m), (n0 + m) & 63);
+          tile_off[m] = __builtin_amdgcn_readlane((int)nlk_word_of(mbase, n0 + m), (n0 + m) & 63);
 #pragma unroll
         for (int m = 0; m < NPX; ++m) {
           if (agg_on) {  // (CH = 3: every lane owns a plane)
@@ -1266,40 +1254,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
           }
         }
     };
-    // Software pipeline over the steps (round 6): a step is one long dependent chain - rows, fold, two stages of
-    // matrix products, shrink, two more stages, unfold, transposition, then four read-modify-writes of the tile one
-    // behind the other (the members overlap: they cannot be reordered) - and pass B kept the FP32 datapath busy
-    // only 59 % of its time against pass A's 80 %. When the first `npipe` members all lie inside the tile (every
-    // temporal target: the tile's halo is the temporal radius) the tile update of step n - 1 stands in the same
-    // basic block as the transforms of step n, so that the scheduler can put the LDS latencies of the one under
-    // the matrix products of the other; two PX buffers swap roles, no copies.
-    int n_start = 0;
-#ifdef NLK_G8_PIPE   // (measured slower - 10 to 15 registers spilled at 168: C2 group 0.711 -> 0.742 ms, profiles/README.md round 6)
-    if constexpr (!G16 && !M5) {
-      const int npipe = min(nagg & ~3, 64);
-      const uint64_t need = npipe >= 64 ? ~0ull : ((1ull << npipe) - 1ull);
-      if (npipe >= 8 && (inside[0] & need) == need) {
-        float PXa[4][4], PXb[4][4];
-        step_px(0, PXa);
-        int n0 = 4;
-        for (; n0 + 4 < npipe; n0 += 8) {
-          step_px(n0, PXb);
-          agg_fast(n0 - 4, PXa);
-          step_px(n0 + 4, PXa);
-          agg_fast(n0, PXb);
-        }
-        if (n0 < npipe) {
-          step_px(n0, PXb);
-          agg_fast(n0 - 4, PXa);
-          agg_fast(n0, PXb);
-        } else {
-          agg_fast(n0 - 4, PXa);
-        }
-        n_start = npipe;
-      }
-    }
-#endif
-    for (int n0 = n_start; n0 < nagg; n0 += MPS) {
+    for (int n0 = 0; n0 < nagg; n0 += MPS) {
       float PX[NPX][4];
       step_px(n0, PX);
       if constexpr (G16) {
@@ -1310,9 +1265,9 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
             const int n = n0 + 4 * t + jm;   // (wave-uniform) the member this round adds
             if (n >= nagg) continue;
             const bool act_img = spl == t, act_w = spl == ((t + 1) & 3);
-            const bool in = ((word_of(inside, n) >> (n & 63)) & 1ull) != 0;
-            const int toff = __builtin_amdgcn_readlane((int)word_of(mbase, n), n & 63);
-            const uint32_t q = __builtin_amdgcn_readlane(word_of(greg, n), n & 63);
+            const bool in = ((nlk_word_of(inside, n) >> (n & 63)) & 1ull) != 0;
+            const int toff = __builtin_amdgcn_readlane((int)nlk_word_of(mbase, n), n & 63);
+            const uint32_t q = __builtin_amdgcn_readlane(nlk_word_of(greg, n), n & 63);
             if (act_img || act_w) {
               float px[4];
 #pragma unroll
@@ -1344,7 +1299,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
         continue;
       }
       // "inside the tile" bits of the step's members (a step of five may straddle the two 64-entry words)
-      uint64_t inb = word_of(inside, n0) >> (n0 & 63);
+      uint64_t inb = nlk_word_of(inside, n0) >> (n0 & 63);
       if constexpr (NR > 1)
         if (NPX > 4 && n0 < 64 && n0 + NPX > 64) inb |= inside[1] << (64 - n0);
       constexpr uint32_t in_all = (1u << NPX) - 1u;
@@ -1355,7 +1310,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
 #pragma unroll
       for (int m = 0; m < NPX; ++m) {
         if (n0 + m >= nagg) break;
-        const uint32_t q = __builtin_amdgcn_readlane(word_of(greg, n0 + m), (n0 + m) & 63);
+        const uint32_t q = __builtin_amdgcn_readlane(nlk_word_of(greg, n0 + m), (n0 + m) & 63);
         const int qx = nlk_x(q), qy = nlk_y(q);
         float px[4] = {PX[m][0], PX[m][1], PX[m][2], PX[m][3]};
         const int lx = qx - rx0, ly = qy - ry0;

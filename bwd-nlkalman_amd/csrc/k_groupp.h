@@ -34,7 +34,7 @@
 
 #include "k_dct12.h"
 #include "k_dct8.h"
-#include "k_group8.h"   // NlkGTile, nlk_f4u, nlk_wave_sum8
+#include "k_group_tile.h"   // NlkGTile, nlk_f4u, nlk_wave_sum8
 #include "k_group8m.h"  // nlk_f4, nlk_bperm
 #include "k_group_math.h"
 #include "nlk_common.h"

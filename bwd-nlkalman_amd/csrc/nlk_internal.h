@@ -14,7 +14,7 @@
 
 struct NlkTvMail;   // k_tvl1.h
 struct NlkTile;     // k_match.h
-struct NlkGTile;    // k_group8.h
+struct NlkGTile;    // k_group_tile.h
 
 struct NlkBuf {
   void* p = nullptr;
