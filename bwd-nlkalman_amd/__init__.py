@@ -40,7 +40,7 @@ HIP_SYMBOLS = [
     "nlk_sigma_default_params", "nlk_dev_estimate_sigma",
     "nlk_curve_default_params", "nlk_dev_estimate_noise_curve", "nlk_vst_scale", "nlk_dev_vst_forward",
     "nlk_dev_vst_inverse", "nlk_dev_noise_affine",
-    "nlk_nlf_build", "nlk_dev_nlf_forward", "nlk_dev_nlf_inverse",
+    "nlk_nlf_build", "nlk_dev_nlf_forward", "nlk_dev_nlf_inverse", "nlk_dev_despike",
     "nlk_yuv_format_from_tag", "nlk_yuv_frame_bytes", "nlk_dev_yuv_to_rgb", "nlk_dev_rgb_to_yuv",
     "nlk_dev_flow_invert", "nlk_bmflow_default_params", "nlk_dev_bm_flow",
     "nlk_dev_probe_add", "nlk_dev_sure_terms", "nlk_sure_mse",
@@ -230,6 +230,7 @@ def hip():
         L.nlk_nlf_build.argtypes = [C.POINTER(NlfTable), vp, i, i, f, f, f]
         for fn in (L.nlk_dev_nlf_forward, L.nlk_dev_nlf_inverse):
             fn.argtypes = [vp, fp, fp, C.c_size_t, i, C.POINTER(NlfTable)]
+        L.nlk_dev_despike.argtypes = [vp, fp, fp, vp, i, i, i, i, f]
         L.nlk_yuv_format_from_tag.argtypes = [C.POINTER(YuvFormat), C.c_char_p]
         L.nlk_yuv_frame_bytes.argtypes = [i, i, C.POINTER(YuvFormat)]
         L.nlk_yuv_frame_bytes.restype = C.c_size_t
@@ -791,6 +792,23 @@ class Context:
     def nlf_inverse(self, d_out, d_in, n, ch, table):
         """The inverse map (algebraic: no unbiasing term)."""
         self._chk(self.L.nlk_dev_nlf_inverse(self.h, d_out, d_in, n, ch, C.byref(table)))
+
+    # ---- defective pixels (include/nlk_hip.h: nlk_dev_despike)
+    def despike(self, d_out, d_in, w, h, ch, thr, radius=1, d_count=None):
+        """d_out = d_in with every sample that lies more than thr outside the range of its ring (its channel's samples
+        at Chebyshev distance `radius`, 1 or 2) replaced by the ring's median, everything else bit for bit (the rule:
+        tests/despike_ref.py). d_out must not be d_in. d_count: None, or ch device uint32 that receive the replaced
+        samples of every channel. Not synchronised."""
+        self._chk(self.L.nlk_dev_despike(self.h, d_out, d_in, d_count, w, h, ch, int(radius), float(thr)))
+
+    def despike_counts(self, d_out, d_in, w, h, ch, thr, radius=1):
+        """despike(), and the replaced samples of every channel ([ch] uint32). Waits for the device."""
+        d = self.alloc(4 * max(ch, 1))
+        try:
+            self.despike(d_out, d_in, w, h, ch, thr, radius, d)
+            return self.download(d, (ch,), np.uint32)
+        finally:
+            self.free(d)
 
     def noise_affine(self, d_out, d_in, n, ch, ab, seed):
         """d_out[i] = d_in[i] + sqrt(max(a_c d_in[i] + b_c, 0)) N_i with awgn's deviates N_i (d_out may be d_in)."""

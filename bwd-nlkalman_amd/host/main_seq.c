@@ -34,7 +34,14 @@
  *           of the run. tvl1 (default): the scripts' TV-L1. bm: block matching (nlk_dev_bm_flow) wherever
  *           a flow is computed - the forward step, the backward pass, the lag-1 smoother's own flow; OPM's FSCALE and TH
  *           apply, DW is ignored. The .flo and mask files hold the flow that was used.
- *   --sure  after --of, in front of the rest, in all three tools (the scripts have no such thing): the error of every
+ *   --despike K[,R]  after --of, in front of --sure, in all three tools (the scripts have no such thing): stuck, hot and dead
+ *           pixels and single-sample impulses are taken out of every noisy frame before the filter sees it
+ *           (nlk_dev_despike): a sample more than K sigma outside the range of its ring (radius R = 1, the
+ *           default, or 2: 2 x 2 blobs) becomes the ring's median. Under SIG = vst | nlf it runs on the transformed frame,
+ *           at the run's sigma; the first frame's measurement (auto, vst, nlf) stays on the frame as read. K = 4 is the
+ *           value DESIGN.md §9's table was made with. The gt tool's noisy files and measures are not touched by it.
+ *           Without the option nothing of this happens: the same launches and allocations as before.
+ *   --sure  after --despike, in front of the rest, in all three tools (the scripts have no such thing): the error of every
  *           flt1 / flt2 frame is estimated without clean frames by Monte-Carlo SURE (seq_sure_step, host/seq_step.h;
  *           DESIGN.md §9): one more FLT1 and FLT2 per frame, on the noisy frame plus a probe of +-eps. OUT/measures-sure
  *           gets, per pass, "F1 I MSE_hat PSNR_hat R/N div" for every frame I and "F1 total ..." (finish_sure), each
@@ -446,7 +453,18 @@ int main(int argc, const char **argv) {
     argv += 2;
     argc -= 2;
   }
-  if (argc > 1 && !strcmp(argv[1], "--sure")) { /* after --of, in front of the rest */
+  float despike_k = 0.f;
+  int despike_r = 1;
+  if (argc > 1 && !strcmp(argv[1], "--despike")) { /* after --of, in front of --sure */
+    if (argc < 3 || seq_despike_parse(argv[2], &despike_k, &despike_r)) {
+      fprintf(stderr, SEQ_DESPIKE_WANT, PROG, argc < 3 ? "" : argv[2]);
+      return 1;
+    }
+    argv[2] = argv[0];
+    argv += 2;
+    argc -= 2;
+  }
+  if (argc > 1 && !strcmp(argv[1], "--sure")) { /* after --despike, in front of the rest */
     S.on = 1;
     argv[1] = argv[0];
     ++argv;
@@ -471,16 +489,25 @@ int main(int argc, const char **argv) {
     if (gt)
       fprintf(stderr, "usage: %s [--of tvl1|bm] [--sure] [--ssim] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
                       "  one-process equivalent of scripts/nlkalman-seq-gt.sh (see the header of main_seq.c)\n"
+                      "  --despike K[,R] (after --of, in front of --sure): a sample more than K sigma outside its ring's range (radius\n"
+                      "  R = 1 | 2) becomes the ring's median before the filter sees the frame: stuck, hot and dead pixels (K = 4: the\n"
+                      "  value of DESIGN.md's table)\n"
                       "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
                       "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
     else if (lsmo)
       fprintf(stderr, "usage: %s [--of tvl1|bm] [--sure] [--flow tvl1|inv] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
                       "  one-process equivalent of scripts/nlkalman-lsmo-seq.sh (see the header of main_seq.c)\n"
+                      "  --despike K[,R] (after --of, in front of --sure): a sample more than K sigma outside its ring's range (radius\n"
+                      "  R = 1 | 2) becomes the ring's median before the filter sees the frame: stuck, hot and dead pixels (K = 4: the\n"
+                      "  value of DESIGN.md's table)\n"
                       "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
                       "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
     else
       fprintf(stderr, "usage: %s [--of tvl1|bm] [--sure] SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]\n"
                       "  one-process equivalent of scripts/nlkalman-seq.sh (see the header of main_seq.c)\n"
+                      "  --despike K[,R] (after --of, in front of --sure): a sample more than K sigma outside its ring's range (radius\n"
+                      "  R = 1 | 2) becomes the ring's median before the filter sees the frame: stuck, hot and dead pixels (K = 4: the\n"
+                      "  value of DESIGN.md's table)\n"
                       "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
                       "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
     return 1;
@@ -642,7 +669,8 @@ int main(int argc, const char **argv) {
     }
     float *n1 = dev_frame(bytes), *n2 = dev_frame(bytes);
     const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .of = of, .sig = &sig, .f1 = &f1, .f2 = &f2,
-                                  .fscale = fs1, .dw = dw1, .th = th1, .work = &W, .d_rgb = d_rgb,
+                                  .fscale = fs1, .dw = dw1, .th = th1, .work = &W,
+                                  .despike_k = despike_k, .despike_r = despike_r, .d_rgb = d_rgb,
                                   .prev_flt1 = t ? flt1 : NULL, .prev_flt2 = t ? flt2[t - 1] : NULL,
                                   .flt1 = n1, .flt2 = n2};
     CHK(seq_forward_step(&step));

@@ -18,6 +18,10 @@
  *     --of tvl1|bm   the flow estimator of the run, as nlkalman-seq's: tvl1 (default), or bm: block matching
  *                    (nlk_dev_bm_flow) for the backward flow and for --smooth tvl1's own flow; --opm's FSCALE and TH
  *                    apply, DW is ignored
+ *     --despike K[,R]   defective pixels (stuck, hot, dead, single-sample impulses) are taken out of every frame before
+ *                    the filter sees it, as nlkalman-seq's --despike (nlk_dev_despike at thr = K sigma, ring radius R = 1,
+ *                    the default, or 2: the 2 x 2 blob a 4:2:0 chroma impulse becomes in RGB). K = 4 is the value
+ *                    DESIGN.md §9's table was made with
  *     --sure         the error of every flt2 frame estimated without clean frames by Monte-Carlo SURE (seq_sure_step,
  *                    host/seq_step.h): one more FLT1 and FLT2 per frame. One stderr line per frame,
  *                    "sure T MSE_hat PSNR_hat R/N div" (T from 1, each value "%.9g", PSNR at 255), and at the end
@@ -189,6 +193,8 @@ static int usage(void) {
           "  --matrix 601|709|auto  --range limited|full|auto  --fpm \"...\"  --opm \"FSCALE DW TH [FSCALE2 DW2 TH2]\"\n"
           "  --smooth tvl1|inv  --spm \"...\"  --frames N  --copy  --probe  -v       (see the header of main_y4m.c)\n"
           "  --of tvl1|bm\n"
+          "  --despike K[,R]  a sample more than K sigma outside its ring's range (radius R = 1 | 2) becomes the ring's median\n"
+          "          before the filter sees the frame: stuck, hot and dead pixels (K = 4: the value of DESIGN.md's table)\n"
           "  --sure  one stderr line per frame, \"sure T MSE_hat PSNR_hat R/N div\": flt2's error estimated without clean\n"
           "          frames (Monte-Carlo SURE; under SIG = vst | nlf in the stabilised domain, at the run's sigma)\n", PROG);
   return 1;
@@ -196,7 +202,7 @@ static int usage(void) {
 
 int main(int argc, const char **argv) {
   const char *matrix_s = "auto", *range_s = "auto", *fpm = "", *opm = "1 0.25 0.75", *pos[3] = {NULL, NULL, NULL};
-  const char *smooth_s = NULL, *spm = "", *of_s = "tvl1";
+  const char *smooth_s = NULL, *spm = "", *of_s = "tvl1", *despike_s = NULL;
   long max_frames = -1;
   int copy = 0, want_probe = 0, verbose = 0, npos = 0, want_sure = 0;
   for (int i = 1; i < argc; ++i) {
@@ -209,6 +215,7 @@ int main(int argc, const char **argv) {
     else if (!strcmp(a, "--smooth")) val = &smooth_s;
     else if (!strcmp(a, "--spm")) val = &spm;
     else if (!strcmp(a, "--of")) val = &of_s;
+    else if (!strcmp(a, "--despike")) val = &despike_s;
     if (val) {
       if (++i >= argc) { fprintf(stderr, "%s: %s needs a value\n", PROG, a); return 1; }
       *val = argv[i];
@@ -251,6 +258,12 @@ int main(int argc, const char **argv) {
   const int of = seq_of_mode(of_s);
   if (of < 0) {
     fprintf(stderr, SEQ_OF_WANT, PROG, of_s);
+    return 1;
+  }
+  float despike_k = 0.f;
+  int despike_r = 1;
+  if (despike_s && seq_despike_parse(despike_s, &despike_k, &despike_r)) {
+    fprintf(stderr, SEQ_DESPIKE_WANT, PROG, despike_s);
     return 1;
   }
   int matrix = 0, range = -1;
@@ -352,7 +365,8 @@ int main(int argc, const char **argv) {
       }
       const int cur = (int)(t & 1), prv = cur ^ 1;
       const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .of = of, .sig = &sig, .f1 = &f1, .f2 = &f2,
-                                    .fscale = fs, .dw = dw, .th = th, .work = &W, .d_rgb = d_rgb,
+                                    .fscale = fs, .dw = dw, .th = th, .work = &W,
+                                    .despike_k = despike_k, .despike_r = despike_r, .d_rgb = d_rgb,
                                     .prev_flt1 = t ? flt1[prv] : NULL, .prev_flt2 = t ? flt2[prv] : NULL,
                                     .flt1 = flt1[cur], .flt2 = flt2[cur]};
       CHK(seq_forward_step(&step));

@@ -1,5 +1,6 @@
-/* seq_args.c — the grammar of the sequence tools' SIG argument (seq_step.h). Plain C: nothing of the device libraries
+/* seq_args.c — the grammar of the sequence tools' SIG argument and of --despike's value (seq_step.h). Plain C: nothing of the device libraries
  * is needed to link it. */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -16,5 +17,19 @@ int seq_sig_parse(const char *text, struct seq_sig *sig) {
   if (!strcmp(text, "auto")) sig->mode = SEQ_SIG_AUTO;
   else if (!strcmp(text, "nlf")) sig->mode = SEQ_SIG_NLF;
   else sig->sigma = atof(text);
+  return 0;
+}
+
+int seq_despike_parse(const char *text, float *k, int *r) {
+  char *end = NULL;
+  const float v = text ? strtof(text, &end) : 0.f;
+  int radius = 1;
+  if (!text || end == text || !isfinite(v) || !(v > 0.f)) return 1;
+  if (*end == ',') { /* ",R": one digit, 1 or 2 */
+    if ((end[1] != '1' && end[1] != '2') || end[2]) return 1;
+    radius = end[1] - '0';
+  } else if (*end) return 1;
+  *k = v;
+  *r = radius;
   return 0;
 }

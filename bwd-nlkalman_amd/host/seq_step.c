@@ -209,7 +209,12 @@ int seq_forward_step(const struct seq_step *s) {
   if (seq_sig_vst(s->sig))
     TRY(nlk_dev_vst_forward(C, s->d_rgb, s->d_rgb, (size_t)w * h * ch, ch, s->sig->vst_ab, s->sig->vst_s));
   if (seq_sig_nlf(s->sig)) TRY(nlk_dev_nlf_forward(C, s->d_rgb, s->d_rgb, (size_t)w * h * ch, ch, &s->sig->nlf));
-  TRY(nlk_d2d(C, k->d_noisy, s->d_rgb, bytes));
+  if (s->despike_k != 0.f) { /* d_noisy = the despiked frame, and d_rgb too: the flow's gray image is made of it */
+    TRY(nlk_dev_despike(C, k->d_noisy, s->d_rgb, NULL, w, h, ch, s->despike_r, s->despike_k * sigma));
+    TRY(nlk_d2d(C, s->d_rgb, k->d_noisy, bytes));
+  } else {
+    TRY(nlk_d2d(C, k->d_noisy, s->d_rgb, bytes));
+  }
   TRY(nlk_dev_rgb2opp(C, k->d_noisy, w, h, ch));
   if (!s->prev_flt2) {
     TRY(nlk_dev_filter_frame(C, s->flt1, k->d_noisy, NULL, NULL, w, h, ch, sigma, s->f1));

@@ -84,6 +84,13 @@ enum {
 int seq_of_mode(const char *name);
 #define SEQ_OF_WANT "%s: --of %s: want tvl1 or bm\n" /* (prog, text) */
 
+/* ---- --despike K[,R]: defective pixels (nlk_dev_despike, include/nlk_hip.h) are taken out of every
+ * noisy frame before the filter sees it, at thr = K sigma and ring radius R. The grammar, nothing else (host/seq_args.c):
+ * "K" or "K,R" with K finite and > 0 and R = 1 or 2 (default 1) -> 0 and *k, *r; anything else: 1, *k and *r as they
+ * were (the caller prints SEQ_DESPIKE_WANT under its own name). K = 4 is the value DESIGN.md §9's table was made with. */
+int seq_despike_parse(const char *text, float *k, int *r);
+#define SEQ_DESPIKE_WANT "%s: --despike %s: want K or K,R with K > 0 and R = 1 or 2\n" /* (prog, text) */
+
 /* ---- one step of the forward recursion */
 struct seq_step {
   nlk_ctx *ctx;
@@ -94,12 +101,16 @@ struct seq_step {
   int fscale;                /* backward flow: finest scale, data weight (lambda) and occlusion threshold */
   float dw, th;
   const struct seq_work *work;
+  float despike_k;           /* 0: off; else the noisy frame is despiked at thr = despike_k * sig->sigma ... */
+  int despike_r;             /* ... and this ring radius (1 or 2) */
   /* per frame: */
-  float *d_rgb;              /* the noisy RGB frame; under vst and nlf it is transformed in place */
+  float *d_rgb;              /* the noisy RGB frame; under vst and nlf it is transformed in place, and despiked likewise */
   const float *prev_flt1, *prev_flt2; /* the previous frame's outputs (opponent space); both NULL on the first frame */
   float *flt1, *flt2;        /* out: this frame's (opponent space) */
 };
-/* variance stabilisation, rgb2opp, then FLT1 and FLT2: spatial on the first frame, afterwards gray -> flow (TV-L1, or
+/* variance stabilisation, then with despike_k != 0 the defective-pixel filter (in the domain where the run's sigma
+ * holds, before rgb2opp and the flow's gray image: nlk_dev_despike into work->d_noisy, which is free at that point, and
+ * a copy back to d_rgb; with despike_k == 0 nothing is launched that was not before), rgb2opp, then FLT1 and FLT2: spatial on the first frame, afterwards gray -> flow (TV-L1, or
  * under SEQ_OF_BM block matching) noisy_t -> flt2_{t-1} -> occlusion mask -> warp + FLT1 -> warp + FLT2 (scripts/nlkalman-seq.sh:39-101).
  * Asynchronous on the context's stream; returns the first failing call's code (nlk_last_error has the message). */
 int seq_forward_step(const struct seq_step *s);
@@ -107,7 +118,8 @@ int seq_forward_step(const struct seq_step *s);
 /* ---- the error estimate of a forward step without clean frames: Monte-Carlo SURE (include/nlk_hip.h: nlk_dev_probe_add,
  * nlk_dev_sure_terms). The noise of frame t is independent of everything before it, so the estimate holds
  * for the recursion's frame t with the previous outputs held fixed; it costs one more FLT1 and FLT2, on a perturbed
- * frame. Under vst / nlf the estimate is in the stabilised domain, at the run's sigma. */
+ * frame. Under vst / nlf the estimate is in the stabilised domain, at the run's sigma. With despike_k != 0 the probe goes
+ * on the frame the filter saw, the despiked one (work->d_noisy): the estimate treats the despiked frame as the data. */
 #define SEQ_SURE_EPS_REL 0.05f /* the probe, in units of sigma: the middle of the plateau 0.025 .. 0.1 of DESIGN.md §9's table */
 #define SEQ_SURE_BLOCK 16      /* the tile of nlk_dev_sure_terms */
 #define SEQ_SURE_FRAME_STEP 0xD1B54A32D192ED03ull /* the seed of frame t = seed + t * this (mod 2^64) */

@@ -68,15 +68,25 @@ class SequenceFilter:
     samples, mse_ch ... div_ch the same per channel (arrays), "flt1" the same dict for flt1, eps and seed as used; and
     .sure_blocks the risk map of flt2, [nby][nbx][ch][2] = (R, D) per sure_block x sure_block tile. sure_seed (default
     0, or NLK_SURE_SEED): frame t uses sure_seed + t * SURE_FRAME_STEP. The estimate is in the domain the filter works
-    in: under sigma="vst" | "nlf" the stabilised one, at .sigma. The smoother's outputs are not estimated."""
+    in: under sigma="vst" | "nlf" the stabilised one, at .sigma. The smoother's outputs are not estimated.
+    despike=K | (K, R): as the tools' --despike K[,R]: every pushed frame goes through Context.despike at
+    thr = K * sigma and ring radius R (1, the default, or 2) after the vst / nlf transform and before anything else
+    sees it (stuck, hot and dead pixels; DESIGN.md §9, whose table was made with K = 4). The pushed frame itself is
+    not modified; sure= then treats the despiked frame as the data. None: nothing is allocated or launched for it."""
 
     LAG1_INVERT_STEPS = 4   # SEQ_LAG1_INVERT_STEPS of host/seq_step.h
     SURE_EPS_REL, SURE_BLOCK, SURE_FRAME_STEP = 0.05, 16, 0xD1B54A32D192ED03   # SEQ_SURE_* of host/seq_step.h
 
     def __init__(self, ctx, w, h, ch, sigma, f1=None, f2=None, s1=None, of_lambda=0.25, of_fscale=1,
                  occ_th=0.75, keep_history=True, lag1=None, lag1_of_lambda=None, lag1_of_fscale=None,
-                 lag1_occ_th=None, of="tvl1", sure=None, sure_seed=None, sure_block=None):
+                 lag1_occ_th=None, of="tvl1", sure=None, sure_seed=None, sure_block=None, despike=None):
         pkg = _p()
+        self.despike, self.d_despiked = None, None
+        if despike is not None:
+            k, r = despike if isinstance(despike, (tuple, list)) else (despike, 1)
+            if not (np.isfinite(float(k)) and float(k) > 0 and r in (1, 2)):
+                raise ValueError(f"SequenceFilter(despike={despike!r}): want None, K or (K, R) with K > 0 and R = 1 or 2")
+            self.despike = (float(k), int(r))
         if of not in ("tvl1", "bm"):
             raise ValueError(f"SequenceFilter(of={of!r}): want 'tvl1' or 'bm'")
         self.flow_estimator = of
@@ -191,6 +201,12 @@ class SequenceFilter:
                 raise ValueError(f"SequenceFilter(sigma='auto'): the first frame gives sigma = {est}")
             self._resolve(est)
         sg = self.sigma
+        if self.despike:
+            if self.d_despiked is None:
+                self.d_despiked = c.alloc(self.nbytes)
+            thr = float(np.float32(self.despike[0]) * np.float32(sg))
+            c.despike(self.d_despiked, d_noisy_rgb, w, h, ch, thr, self.despike[1])
+            d_noisy_rgb = self.d_despiked   # the flow sees the despiked frame too
         c.d2d(self.d_noisy, d_noisy_rgb, self.nbytes)
         c.rgb2opp(self.d_noisy, w, h, ch)
         n1, n2 = self._frame(), self._frame()

@@ -45,6 +45,7 @@
  *                                       nothing: the reference measures against clean frames only
  *   nlk_dev_yuv_to_rgb / nlk_dev_rgb_to_yuv, nlk_yuv_format_from_tag, nlk_yuv_frame_bytes
  *                                       nothing: the reference reads and writes RGB image files only
+ *   nlk_dev_despike                     nothing: the reference has no counterpart (it models Gaussian noise only)
  */
 #ifndef NLK_HIP_H
 #define NLK_HIP_H
@@ -453,6 +454,27 @@ int nlk_nlf_build(struct nlk_nlf_table *t, const struct nlk_curve_bin *bins, int
                   float rho);
 int nlk_dev_nlf_forward(nlk_ctx *ctx, float *out, const float *in, size_t n, int ch, const struct nlk_nlf_table *t);
 int nlk_dev_nlf_inverse(nlk_ctx *ctx, float *out, const float *in, size_t n, int ch, const struct nlk_nlf_table *t);
+
+/* ---- defective pixels (stuck, hot and dead sensor sites, single-sample impulses: DESIGN.md §9; the rule is stated in
+ * float32 numpy by tests/despike_ref.py). Every channel of the HWC image by itself:
+ *   ring of (x, y)   the samples at Chebyshev distance exactly `radius`: 8 values for radius 1, 16 for radius 2
+ *   border indices   along an axis of n samples: j = |i|; j = 2 (n - 1) - j if j >= n; then clamped to [0, n - 1] (a
+ *                    reflection that does not repeat the edge; a 1 x 1 image is its own ring and is never changed)
+ *   mn, mx           the ring's minimum and maximum; lo, hi its two middle order statistics (4th and 5th of 8, 8th and
+ *                    9th of 16); med = (lo + hi) * 0.5f, one rounding each
+ *   hit              v > mx + thr or v < mn - thr, one float add / subtract each: out = med. Anything else is copied bit
+ *                    for bit, and so is a sample that is non-finite or whose ring holds a non-finite value
+ * -0 and +0 compare equal; the sign of a replaced value that equals zero is unspecified. radius 2 is for an impulse
+ * that reaches the RGB frame as a 2 x 2 blob (a chroma sample of a 4:2:0 stream, a defect that went through a
+ * demosaic): no pixel of such a blob has another on its distance-2 ring. A blob on the border reflects onto itself and
+ * is partly missed: a stated limit.
+ * d_count: NULL, or ch device words: the call zeroes them and adds the replaced samples of every channel with integer
+ * atomics (order-free: the same bits on every call, like the image). Asynchronous on the context's stream. NLK_EINVAL
+ * for w or h < 1, ch outside 1..16, a radius other than 1 and 2, a thr that is not finite and >= 0, a NULL ctx, out or
+ * in, and out == in (the stencil reads its neighbours): nothing is written and the context keeps working. NLK_EUNSUP
+ * for a row of 2^31 floats or more. */
+int nlk_dev_despike(nlk_ctx *ctx, float *out, const float *in, uint32_t *d_count, int w, int h, int ch, int radius,
+                    float thr);
 
 /* nlk_dev_awgn with a deviation that follows the signal: out[i] = (float)((double)in[i] + sqrt(max(a_c in[i] + b_c,
  * 0)) g_i), c = i mod ch, g_i exactly the normal deviate nlk_dev_awgn draws for that index and seed; ab as above
