@@ -5,113 +5,24 @@
 // In the reference a target is skipped when an EARLIER, non-skipped target's
 // group contained it. Whether a target is skipped therefore depends only on
 // integer records (group coordinates, np0) that the matching kernel already
-// produced for every target, not on any filtered pixel. Five replays, all exact:
+// produced for every target, not on any filtered pixel. Four replays, all exact:
 //   k_mask_commit_rows1   reach 1 (the steady state of the pipelines): one grid ROW per step on bit
 //                         planes, a carry chain per row solved word-parallel (below)
 //   k_mask_commit_rows<R> reach 2 and 3 (first frames of 8 x 8 patches, 12 x 12 patches): one grid row per step, the
 //                         chain inside the row solved by iteration to its fixed point
 //   k_mask_commit_wave<R> reach <= 3: anti-diagonal wavefront, lane = grid row, marks handed down by DPP (grids wider
 //                         than 2048 targets, NLK_COMMIT_WAVE=1)
-//   k_mask_commit<RPT>    the same wavefront with the mask as an LDS bitmap (first version, kept
-//                         for comparison)
 //   k_mask_commit_lists   any reach, from the group-coordinate lists
 // The wavefront replays: a marking group reaches at most R grid cells, so target (i, j) can be decided
-// at time i + (R+1)*j, when every target that can mark it has already been decided. k_mask_commit:
-// one workgroup, one thread per grid row (RPT rows when the grid has more than 1024 rows), one barrier
-// per time step.
-//
-// The mask lives in LDS as one bit per grid target (only grid-aligned
-// coordinates are ever tested). Only FORWARD marks (targets later in raster
-// order) are applied: a bit is then only ever set by targets decided before
-// its owner, so the final bit array IS the skip decision and nothing is
-// written to HBM inside the loop.
+// at time i + (R+1)*j, when every target that can mark it has already been decided.
+// The launches, and the scratch they work in: tu_commit.hip.
 #pragma once
 #include "nlk_common.h"
 #include "k_commit_rows.h"
 
-template <int RPT>  // grid rows per thread: row j = threadIdx.x + r * blockDim.x
-__global__ void __launch_bounds__(1024)
-k_mask_commit(const uint64_t* __restrict__ marks, uint8_t* __restrict__ active, int ngx,
-              int ngy, int R) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  uint32_t* bits = (uint32_t*)smem;
-  const int ntot = ngx * ngy;
-  // + a tail: marks aimed below the last grid row (strip mode) land in padding
-  const int nwords = (ntot + (R + 1) * ngx + 63) / 32 + 1;
-  for (int i = threadIdx.x; i < nwords; i += blockDim.x) bits[i] = 0;
-  __syncthreads();
-  const int side = 2 * R + 1;
-  const int skew = R + 1;
-  const int nsteps = ngx + skew * (ngy - 1);
-  auto fetch = [&](int j, int s) -> uint64_t {
-    const int i = s - skew * j;
-    return (j < ngy && i >= 0 && i < ngx) ? marks[(size_t)j * ngx + i] : 0ull;
-  };
-  // Decide the targets of time step s; mw = their mark words. Bit
-  // (dj+R)*side + (di+R) of a mark word stands for the grid neighbour (di, dj);
-  // the raster-forward neighbours are exactly the bits above the centre bit. Each
-  // forward row of (up to) `side` neighbours is OR-ed into the bit array with at
-  // most two 32-bit LDS atomics: no per-bit loop, no division.
-  const int centre = R * side + R;
-  const uint32_t rowmask = (1u << side) - 1u;
-  // LDS atomics retire about one lane per clock on gfx950, so they are issued
-  // only by the lanes that really have a bit to set.
-  auto or_bits = [&](int pos, uint32_t mask) {  // bits[pos ...] |= mask
-    const int wd = pos >> 5, sh = pos & 31;
-    const uint64_t m2 = (uint64_t)mask << sh;
-    if ((uint32_t)m2) atomicOr(&bits[wd], (uint32_t)m2);
-    if ((uint32_t)(m2 >> 32)) atomicOr(&bits[wd + 1], (uint32_t)(m2 >> 32));
-  };
-  auto decide = [&](int s, const uint64_t (&mw)[RPT]) {
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) {
-      const int j = threadIdx.x + r * blockDim.x;
-      const int i = s - skew * j;
-      const bool in = j < ngy && i >= 0 && i < ngx;
-      const int t = in ? j * ngx + i : 0;
-      const bool done = (bits[t >> 5] >> (t & 31)) & 1u;
-      const uint64_t fwd = (in && !done) ? (mw[r] >> (centre + 1)) : 0ull;
-      or_bits(t + 1, (uint32_t)fwd & ((1u << R) - 1u));          // same row, di = 1..R
-      for (int dj = 1; dj <= R; ++dj)                              // rows below, di = -R..R
-        or_bits(t + dj * ngx - R, (uint32_t)(fwd >> (R + (dj - 1) * side)) & rowmask);
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): LDS atomics issued; loads stay in flight
-    __builtin_amdgcn_s_barrier();
-  };
-  // The mark words of a row are consumed one per step. They are streamed in
-  // phases of S steps: while phase p is decided from registers A, the loads of
-  // phase p+1 into B are in flight, so no HBM latency sits between barriers.
-  constexpr int S = 16;
-  uint64_t A[RPT][S], B[RPT][S];
-#pragma unroll
-  for (int r = 0; r < RPT; ++r)
-#pragma unroll
-    for (int e = 0; e < S; ++e) A[r][e] = fetch(threadIdx.x + r * blockDim.x, e);
-  for (int s0 = 0; s0 < nsteps; s0 += S) {
-#pragma unroll
-    for (int r = 0; r < RPT; ++r)
-#pragma unroll
-      for (int e = 0; e < S; ++e) B[r][e] = fetch(threadIdx.x + r * blockDim.x, s0 + S + e);
-#pragma unroll
-    for (int e = 0; e < S; ++e) {
-      uint64_t mw[RPT];
-#pragma unroll
-      for (int r = 0; r < RPT; ++r) mw[r] = A[r][e];
-      decide(s0 + e, mw);
-    }
-#pragma unroll
-    for (int r = 0; r < RPT; ++r)
-#pragma unroll
-      for (int e = 0; e < S; ++e) A[r][e] = B[r][e];
-  }
-  __syncthreads();
-  for (int t = threadIdx.x; t < ntot; t += blockDim.x)
-    active[t] = !((bits[t >> 5] >> (t & 31)) & 1u);
-}
-
 // ---------------------------------------------------------------------------
-// Register-resident variant (patch grids of up to 1024 rows): no LDS mask, no
-// barrier. Lane = grid row; the marks a row receives from the R rows above are
+// The diagonal replay (up to 1024 grid rows per launch): the mask in registers,
+// no barrier. Lane = grid row; the marks a row receives from the R rows above are
 // 2R+1-bit row masks that travel lane -> lane+1 by DPP (wave_shr:1) and are
 // OR-ed into a small per-lane shift register of pending marks for the next
 // (R+1)^2 columns; a row's own forward marks go into the same register. Only
@@ -119,7 +30,7 @@ k_mask_commit(const uint64_t* __restrict__ marks, uint8_t* __restrict__ active, 
 // the next wavefront (which runs one phase of 16 steps behind) polls a progress
 // word once per phase before consuming them. A step is 13 branch-free instructions on
 // 32-bit registers (the forward bits of the mark words arrive pre-shifted and ordered by step from
-// k_marks_skew) instead of an LDS round trip + atomics + workgroup barrier.
+// k_marks_skew).
 // ---------------------------------------------------------------------------
 #define NLK_CW_RING 128  // steps of edge data kept per wavefront
 #ifndef NLK_CW_PHASE
@@ -299,7 +210,7 @@ k_marks_planes1(const uint64_t* __restrict__ marks, uint32_t* __restrict__ plane
 __global__ void __launch_bounds__(64)
 k_mask_commit_rows1(const uint32_t* __restrict__ planes, uint32_t* __restrict__ actbits,
                     uint32_t* __restrict__ astate, int ngx, int first, int nrows) {
-  nlk_commit_rows1<NLK_CR_BATCH, false>(planes, actbits, astate, nullptr, 0u, ngx, first, nrows, threadIdx.x);
+  nlk_commit_rows1<nlk_plane_layout(1).batch, false>(planes, actbits, astate, nullptr, 0u, ngx, first, nrows, threadIdx.x);
 }
 
 // the decision bits of tagged words -> the byte per target (records, on request: nlk_ctx_read_records)

@@ -5,6 +5,21 @@
 #include "nlk_common.h"
 
 #define NLK_CR_BATCH 16  // rows per batch: the next batch's planes load while this one is replayed
+
+// The bit-plane scratch of the row replays, stated once for the kernels below and for the host that sizes the arrays
+// (tu_commit.hip): planes[(j * np + p) * 64 + word] for the grid rows j.
+struct NlkPlaneLayout {
+  int np;     // planes per grid row: the R marks to the right in the row, then 2R+1 for each of the R rows below (reach 1: 4)
+  int batch;  // rows whose planes are in flight together, in each of two register sets (the kernels' PF)
+  // The rows the arrays hold. Whole batches: a batch is loaded and, at reach 1, replayed without predicates, so a
+  // band's last batch runs into the rows of the next band or past the grid. Three batches more: the loop loads up to
+  // two batches beyond the one it replays, and a row's states are stored at the row after it.
+  constexpr int rows_pad(int rows) const { return (rows + batch - 1) / batch * batch + 3 * batch; }
+};
+constexpr NlkPlaneLayout nlk_plane_layout(int R) {
+  return {R + R * (2 * R + 1), R == 1 ? NLK_CR_BATCH : 48 / (R + R * (2 * R + 1))};
+}
+
 // Rows [first, first + nrows) of the grid; the only state a row hands to the next - `a`, the columns marked
 // from above - is kept per row in `astate` (row j's input at astate[j]), so that a grid replayed in bands
 // (one call per band, in order) continues where the band before stopped.
@@ -85,19 +100,13 @@ __device__ __forceinline__ void nlk_commit_rows1(const uint32_t* __restrict__ pl
 }
 
 // ---- reach 2 and 3: the same by iteration inside the row (formulation: k_commit.h)
-template <int R>
-struct NlkCommitRows {
-  static constexpr int side = 2 * R + 1, NP = R + R * side;
-  static constexpr int PF = 48 / NP;  // rows per batch of planes in flight (two register sets)
-};
-
 // astate[(j * R + k) * 64 + word]: the marks rows j-1, j-2, .. have left for row j + k when row j starts.
 // TAG: decisions as generation-tagged words for consumers that poll (see nlk_commit_rows1), whole grid only.
 template <int R, bool TAG>
 __device__ __forceinline__ void nlk_commit_rows(const uint32_t* __restrict__ planes, uint32_t* __restrict__ actbits,
                                                 uint32_t* __restrict__ astate, uint64_t* __restrict__ tagged,
                                                 uint32_t generation, int ngx, int first, int nrows, int lane) {
-  constexpr int side = 2 * R + 1, NP = R + R * side, PF = NlkCommitRows<R>::PF;
+  constexpr int side = 2 * R + 1, NP = nlk_plane_layout(R).np, PF = nlk_plane_layout(R).batch;
   const int nb = ngx - 32 * lane;
   const uint32_t colmask = nb <= 0 ? 0u : (nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u));
   auto from_prev = [](uint32_t v) {

@@ -18,7 +18,6 @@ namespace nlk_host12 {
 #undef NLK_HD
 }  // namespace nlk_host12
 
-#include "k_commit.h"
 #include "k_frame.h"
 #include "k_match.h"   // NlkTile (the kernels themselves are compiled in tu_match.hip)
 #include "nlk_internal.h"
@@ -508,7 +507,7 @@ static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* pr
   // temporal frame only groups with a valid previous patch mark (reference: :931)
   // and those searched with the temporal radius (reference: :637)
   const int wmark = (g.smoother || g.have_prev) ? g.wsz_t : g.wsz_x;
-  g.R = wmark / g.step;  // (R > 3: the mask replay runs from the coordinate lists, commit_rows)
+  g.R = wmark / g.step;  // (R > 3: the mask replay runs from the coordinate lists, tu_commit.hip)
   const int ncand = (2 * wmax + 1) * (2 * wmax + 1);
   // the tiled matching kernels exist for patch sizes 4 / 6 / 8 / 10 / 12 / 16, 1 or 3 channels and
   // windows of up to 1024 candidates; everything else the reference accepts goes to k_bm_generic
@@ -660,107 +659,6 @@ static int match_rows(nlk_ctx* c, const NlkPlan& pl, hipStream_t stream, int r0,
   return rc;
 }
 
-// The bit-plane scratch of the row replay (k_commit_rows.h assumes exactly this): planes per grid row, rows per
-// batch, and the rows the arrays hold - whole batches (a band's last batch may run into the rows of the next) + 3
-struct NlkPlaneLayout {
-  int np, batch, rows_pad;
-};
-static NlkPlaneLayout plane_layout(int R, int rows) {
-  const int np = R + R * (2 * R + 1);  // (reach 1: 4)
-  const int batch = R == 1 ? NLK_CR_BATCH : 48 / np;
-  return {np, batch, (rows + batch - 1) / batch * batch + 3 * batch};
-}
-
-// the bit planes of the grid rows [first, first + nrows) from their mark words (reach 1..3); `gen`: the in-launch
-// replay's generation counter, advanced by the kernel (else nullptr)
-static void launch_marks_planes(hipStream_t stream, int R, const uint64_t* marks, uint32_t* planes, int ngx, int first,
-                                int nrows, uint32_t* gen) {
-  auto kern = R == 1 ? k_marks_planes1 : (R == 2 ? k_marks_planes<2> : k_marks_planes<3>);
-  hipLaunchKernelGGL(kern, dim3(8, nrows), dim3(256), 0, stream, marks, planes, ngx, first, gen);
-}
-
-// phase 2: replay of the raster-order processed mask over the mark words of the grid rows
-// [first, first + rows) (`marks` / `active` = whole-grid arrays). Rows before `first` are context:
-// their decisions must be final in `active`.
-// `total` = rows of the whole grid when it is replayed band by band (first > 0 continues the band before).
-static int commit_rows(nlk_ctx* c, hipStream_t stream, const uint64_t* marks, uint8_t* active, int ngx, int first,
-                       int nrows, int R, int total = 0) {
-  total = max(total, first + nrows);
-  if (R == 0) {
-    // a group cannot reach another grid target: nothing is ever skipped
-    HIPCHK(c, hipMemsetAsync(active + (size_t)first * ngx, 1, (size_t)nrows * ngx, stream));
-    return NLK_OK;
-  }
-  if (R <= 3 && ngx <= 2048 && !nlk_set(c->sw.commit_wave) && !nlk_set(c->sw.commit_lds) && !nlk_set(c->sw.commit_band)) {
-    // one grid row per step on bit planes (k_commit.h; reach 2 / 3: the in-row chain solved by iteration); the
-    // arrays cover the whole grid: the planes, then per row the decisions (64 words) and the row states (R x 64)
-    const NlkPlaneLayout L = plane_layout(R, total);
-    int rc = reserve(c, c->skew, sizeof(uint32_t) * (size_t)L.rows_pad * (L.np + 1 + R) * 64);
-    if (rc) return rc;
-    uint32_t* planes = (uint32_t*)c->skew.p;
-    uint32_t* actbits = planes + (size_t)L.rows_pad * L.np * 64;
-    uint32_t* astate = actbits + (size_t)L.rows_pad * 64;
-    launch_marks_planes(stream, R, marks, planes, ngx, first, nrows, nullptr);
-    hipLaunchKernelGGL(R == 1 ? k_mask_commit_rows1 : (R == 2 ? k_mask_commit_rows<2> : k_mask_commit_rows<3>), dim3(1),
-                       dim3(64), 0, stream, (const uint32_t*)planes, actbits, astate, ngx, first, nrows);
-    hipLaunchKernelGGL(k_active_bytes, dim3((ngx + 255) / 256, nrows), dim3(256), 0, stream, (const uint32_t*)actbits,
-                       active, ngx, first);
-    HIPCHK(c, hipGetLastError());
-    return NLK_OK;
-  }
-  if (R <= 3 && (first != 0 || !nlk_set(c->sw.commit_lds))) {
-    // one lane per grid row, up to 1024 rows per launch; more rows in pieces that start with the
-    // previous piece's last R rows as context (k_commit.h)
-    int band = nlk_or(c->sw.commit_band, 1024);
-    band = band < 2 * R + 2 ? 2 * R + 2 : (band > 1024 ? 1024 : band);
-    auto pre = R == 1 ? k_marks_skew<1> : (R == 2 ? k_marks_skew<2> : k_marks_skew<3>);
-    auto kern = R == 1 ? k_mask_commit_wave<1> : (R == 2 ? k_mask_commit_wave<2> : k_mask_commit_wave<3>);
-    const int end = first + nrows;
-    for (int f = first; f < end;) {  // `f` = first row this piece decides
-      const int ctx = f == 0 ? 0 : R;
-      const int r0 = f - ctx, rows = min(band, end - r0);
-      const int threads = ((rows + 63) / 64) * 64;
-      const int nsteps = ngx + (R + 1) * (rows - 1);
-      const size_t sk_bytes = sizeof(uint32_t) * (size_t)(nsteps + 3 * NLK_CW_PHASE) * threads;
-      int rc = reserve(c, c->skew, sk_bytes);
-      if (rc) return rc;
-      HIPCHK(c, hipMemsetAsync(c->skew.p, 0, sk_bytes, stream));
-      hipLaunchKernelGGL(pre, dim3((rows * ngx + 255) / 256), dim3(256), 0, stream, marks + (size_t)r0 * ngx,
-                         (uint32_t*)c->skew.p, ngx, rows, threads, (const uint8_t*)active + (size_t)r0 * ngx, ctx);
-      hipLaunchKernelGGL(kern, dim3(1), dim3(threads), 0, stream, (const uint32_t*)c->skew.p,
-                         active + (size_t)r0 * ngx, ngx, rows, ctx);
-      f = r0 + rows;
-    }
-    HIPCHK(c, hipGetLastError());
-    return NLK_OK;
-  }
-  if (first != 0) return fail(c, NLK_EINVAL, "the LDS / list mask replays take whole grids only");
-  const int ngy = nrows, ngrid = ngx * ngy;
-  if (R > 3) {
-    // (2R+1)^2 neighbours do not fit the 64-bit mark words: replay from the group-coordinate lists of
-    // the match phase that has just run in this context (k_mask_commit_lists)
-    const NlkGeom& lg = c->last.g;
-    if (!c->last.valid || lg.ngx != ngx || lg.ngy != ngy || lg.R != R || marks != (const uint64_t*)c->marks.p)
-      return fail(c, NLK_EUNSUP, "group reach %d grid cells > 3: the mask replay needs the coordinate lists of the "
-                  "context's own match phase (row strips across GPUs are limited to reach 3)", R);
-    hipLaunchKernelGGL(k_mask_commit_lists, dim3(1), dim3(1024), 0, stream, (const NlkTarget*)c->tinfo.p,
-                       (const uint32_t*)c->gcoords.p, lg.gstride, active, ngx, ngy, R, lg.step, lg.oy);
-    HIPCHK(c, hipGetLastError());
-    return NLK_OK;
-  }
-  const int rpt = (ngy + 1023) / 1024;
-  const int threads = min(1024, ((ngy + 63) / 64) * 64);
-  const size_t bits = sizeof(uint32_t) * ((size_t)(ngrid + (R + 1) * ngx + 63) / 32 + 1);
-  if (bits > 160 * 1024 || rpt > 4)
-    return fail(c, NLK_EUNSUP, "patch grid %dx%d too large for the mask replay", ngx, ngy);
-  auto kern = rpt == 1 ? k_mask_commit<1> : (rpt == 2 ? k_mask_commit<2> : k_mask_commit<4>);
-  HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bits));
-  hipLaunchKernelGGL(kern, dim3(1), dim3(threads), bits, stream, marks, active, ngx, ngy, R);
-  HIPCHK(c, hipGetLastError());
-  return NLK_OK;
-}
-
 // The mask replay inside the group kernel's launch (k_group8m.h, NlkGTile::chase): the replay of a grid is a chain
 // of ~270 dependent row steps on ONE wavefront (reach 1: 24 us of a 1.1 ms frame at 1080p, reach 2: 80 us of a 2 ms
 // first frame, the rest of the chip idle) that stays far ahead of the group kernel's own progress through the rows
@@ -770,24 +668,8 @@ static int commit_rows(nlk_ctx* c, hipStream_t stream, const uint64_t* marks, ui
 static bool chase_selected(const nlk_ctx* c, const NlkGeom& g) {
   return g.R >= 1 && g.R <= 3 && g.ngx <= 2048 && g.psz == 8 && (g.ch == 1 || g.ch == 3) && g.kmax <= 128 && g.gstride <= 128 &&
          !c->deterministic && c->planes.cap < ((size_t)1 << 32) && !nlk_set(c->sw.no_chase) &&
-         !nlk_set(c->sw.commit_wave) && !nlk_set(c->sw.commit_lds) && !nlk_set(c->sw.commit_band) &&
+         !nlk_set(c->sw.commit_wave) && !nlk_set(c->sw.commit_band) &&
          !nlk_set(c->sw.generic_group) && !nlk_set(c->sw.group_packed) && !nlk_set(c->sw.group_dpp);
-}
-
-// bit planes of the grid rows [0, nrows) + a fresh generation of tagged words (the counter lives on the device and
-// is advanced by the bit-plane kernel: a step captured into a HIP graph gets a new generation at every replay)
-static int chase_prepare(nlk_ctx* c, hipStream_t stream, const uint64_t* marks, int ngx, int nrows, int R) {
-  const NlkPlaneLayout L = plane_layout(R, nrows);
-  int rc = reserve(c, c->skew, sizeof(uint32_t) * (size_t)L.rows_pad * L.np * 64);
-  if (rc) return rc;
-  const size_t wbytes = sizeof(uint64_t) * (size_t)(nrows + 4 * NLK_CR_BATCH + 1) * 64;
-  if (wbytes > c->chase.cap) {
-    if ((rc = reserve(c, c->chase, wbytes))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->chase.p, 0, c->chase.cap, stream));  // (generation 0; no word of another life carries one)
-  }
-  launch_marks_planes(stream, R, marks, (uint32_t*)c->skew.p, ngx, 0, nrows, (uint32_t*)c->chase.p);
-  HIPCHK(c, hipGetLastError());
-  return NLK_OK;
 }
 
 // phase 3 for the target rows [r0, r0 + rows) of the last plan (c->last); `chase`: the mask replay the launch is
@@ -805,11 +687,10 @@ static int group_rows(nlk_ctx* c, hipStream_t stream, float* acc, const uint8_t*
 // stay tagged words; nlk_ctx_flush_active expands them into `lazy_dst` (nullptr: the context's own array) on demand.
 static int chase_group(nlk_ctx* c, float* acc, const uint64_t* marks, const uint8_t* active_rows, int ngx, int row0,
                        int rows, int R, unsigned char* lazy_dst) {
-  int rc = chase_prepare(c, c->stream, marks, ngx, rows, R);
+  NlkChase chase;
+  int rc = nlk_chase_prepare(c, c->stream, marks, ngx, row0, rows, R, &chase);
   if (rc) return rc;
   mark(c, 3);
-  const uint32_t* gen = (const uint32_t*)c->chase.p;  // ([0] the generation counter, from word 64 on the tagged words)
-  const NlkChase chase = {(const uint32_t*)c->skew.p, (uint64_t*)c->chase.p + 64, gen, R, row0, rows};
   if ((rc = group_rows(c, c->stream, acc, active_rows, 0, c->last.g.ngy, 0, &chase))) return rc;
   nlk_set_lazy_active(c, ngx, rows, lazy_dst);
   mark(c, 4);
@@ -856,20 +737,15 @@ static int frame_accumulate(nlk_ctx* c, float* acc, const float* cur, const floa
     mark(c, 2);
     if (chase_selected(c, g))  // (the bytes of `active` only when somebody reads the records)
       return chase_group(c, acc, (const uint64_t*)c->marks.p, active, g.ngx, 0, g.ngy, g.R, nullptr);
-    if ((rc = commit_rows(c, c->stream, (const uint64_t*)c->marks.p, active, g.ngx, 0, g.ngy, g.R))) return rc;
+    if ((rc = nlk_launch_commit(c, c->stream, (const uint64_t*)c->marks.p, active, g.ngx, 0, g.ngy, g.R))) return rc;
     mark(c, 3);
     if ((rc = group_rows(c, c->stream, acc, active, 0, g.ngy, 0))) return rc;
     mark(c, 4);
     return NLK_OK;
   }
   // ---- banded on two streams. Band b runs on stream b & 1; its mask replay waits for band b-1's.
-  // (the replay's scratch is sized for the largest piece now: growing it between two bands would
-  // synchronise the device)
-  {
-    const int rows = min(1024, (g.ngy + nb - 1) / nb + g.R + 1), threads = ((rows + 63) / 64) * 64;
-    const size_t need = sizeof(uint32_t) * (size_t)(g.ngx + (g.R + 1) * (rows - 1) + 3 * NLK_CW_PHASE) * threads;
-    if ((rc = reserve(c, c->skew, need))) return rc;
-  }
+  // (the replay's scratch for every band now: growing it between two bands would synchronise the device)
+  if ((rc = nlk_commit_reserve(c, g.ngx, g.R, g.ngy, nb))) return rc;
   hipStream_t st[2] = {c->stream, c->aux_stream};
   hipEvent_t* ev = c->sync_ev;  // [0] layout done, [1] / [2] replay of the last even / odd band done, [3] aux stream done
   HIPCHK(c, hipEventRecord(ev[0], st[0]));
@@ -881,7 +757,7 @@ static int frame_accumulate(nlk_ctx* c, float* acc, const float* cur, const floa
   for (int b = 0; b < nb; ++b) {
     hipStream_t s = st[b & 1];
     if (b > 0) HIPCHK(c, hipStreamWaitEvent(s, ev[1 + ((b - 1) & 1)], 0));
-    if ((rc = commit_rows(c, s, (const uint64_t*)c->marks.p, active, g.ngx, r0[b], r0[b + 1] - r0[b], g.R, g.ngy))) return rc;
+    if ((rc = nlk_launch_commit(c, s, (const uint64_t*)c->marks.p, active, g.ngx, r0[b], r0[b + 1] - r0[b], g.R, g.ngy))) return rc;
     HIPCHK(c, hipEventRecord(ev[1 + (b & 1)], s));
     if ((rc = group_rows(c, s, acc, active + (size_t)r0[b] * g.ngx, r0[b], r0[b + 1] - r0[b], b))) return rc;
   }
@@ -950,7 +826,7 @@ int nlk_dev_mask_commit(nlk_ctx* c, const void* marks, int ngx, int ngy, int rea
   if (!c || !marks || !active || ngx < 1 || ngy < 1 || reach < 0)
     return fail(c, NLK_EINVAL, "bad mask-commit arguments");
   NLK_USE_DEVICE(c);
-  int rc = commit_rows(c, c->stream, (const uint64_t*)marks, active, ngx, 0, ngy, reach);
+  int rc = nlk_launch_commit(c, c->stream, (const uint64_t*)marks, active, ngx, 0, ngy, reach);
   mark(c, 3);
   return rc;
 }
@@ -977,7 +853,7 @@ int nlk_dev_strip_commit_group(nlk_ctx* c, float* acc, const void* marks, int ng
   NLK_USE_DEVICE(c);
   if (reach == g.R && chase_selected(c, g))  // (nlk_ctx_flush_active: rows [0, gy0 + g.ngy) of `active`)
     return chase_group(c, acc, (const uint64_t*)marks, active + (size_t)gy0 * ngx, ngx, gy0, gy0 + g.ngy, reach, active);
-  int rc = commit_rows(c, c->stream, (const uint64_t*)marks, active, ngx, 0, ngy, reach);
+  int rc = nlk_launch_commit(c, c->stream, (const uint64_t*)marks, active, ngx, 0, ngy, reach);
   if (rc) return rc;
   mark(c, 3);
   rc = group_rows(c, c->stream, acc, active + (size_t)gy0 * ngx, 0, g.ngy, 0);
@@ -1082,6 +958,8 @@ static int frame_host(nlk_ctx* c, float* out_h, const float* cur_h, const float*
   if ((rc = plan_frame(c, pl, d_cur, d_prev, d_basic, w, h, ch, sigma, P, 0, ngy, smoother, 8, nullptr, false))) return rc;
   const NlkGeom& g = pl.g;
   uint8_t* active = (uint8_t*)c->active.p;
+  // (the replay's scratch for every band, before the first band is in flight)
+  if ((rc = nlk_commit_reserve(c, g.ngx, g.R, g.ngy, nb))) return rc;
   // the streams start behind whatever the context's stream was doing (the device images are reused call to call)
   HIPCHK(c, hipEventRecord(c->sync_ev[0], c->stream));
   HIPCHK(c, hipStreamWaitEvent(c->up_stream, c->sync_ev[0], 0));
@@ -1114,7 +992,7 @@ static int frame_host(nlk_ctx* c, float* out_h, const float* cur_h, const float*
     HIPCHK(c, hipEventRecord(c->band_ev[E_LAY][b], s));
     if ((rc = match_rows(c, pl, s, r0, r1 - r0, b))) return rc;
     if (b > 0) HIPCHK(c, hipStreamWaitEvent(s, c->band_ev[E_MASK][b - 1], 0));
-    if ((rc = commit_rows(c, s, (const uint64_t*)c->marks.p, active, g.ngx, r0, r1 - r0, g.R, g.ngy))) return rc;
+    if ((rc = nlk_launch_commit(c, s, (const uint64_t*)c->marks.p, active, g.ngx, r0, r1 - r0, g.R, g.ngy))) return rc;
     HIPCHK(c, hipEventRecord(c->band_ev[E_MASK][b], s));
     if ((rc = group_rows(c, s, acc, active + (size_t)r0 * g.ngx, r0, r1 - r0, b))) return rc;
     HIPCHK(c, hipEventRecord(c->band_ev[E_GRP][b], s));
@@ -1225,9 +1103,8 @@ int nlk_ctx_flush_active(nlk_ctx* c) {
   if (!c) return fail(nullptr, NLK_EINVAL, "null context");
   if (!nlk_active_is_lazy(c)) return NLK_OK;
   NLK_USE_DEVICE(c);
-  hipLaunchKernelGGL(k_active_bytes_tagged, dim3((c->lazy_ngx + 255) / 256, c->lazy_ngy), dim3(256), 0, c->stream,
-                     (const uint64_t*)c->chase.p + 64, c->lazy_dst ? c->lazy_dst : (uint8_t*)c->active.p, c->lazy_ngx);
-  HIPCHK(c, hipGetLastError());
+  int rc = nlk_launch_active_tagged(c, c->stream, c->lazy_dst ? c->lazy_dst : (uint8_t*)c->active.p, c->lazy_ngx, c->lazy_ngy);
+  if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   nlk_set_lazy_active(c, 0, 0, nullptr);
   return NLK_OK;

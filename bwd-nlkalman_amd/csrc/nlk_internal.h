@@ -53,7 +53,7 @@ struct NlkRecView {
   X(deterministic, "NLK_DETERMINISTIC") X(generic_group, "NLK_GENERIC_GROUP") X(group_packed, "NLK_GROUP_PACKED") \
   X(group_dpp, "NLK_GROUP_DPP") X(group_sep, "NLK_GROUP_SEP") X(group_ilp, "NLK_GROUP_ILP") X(generic_match, "NLK_GENERIC_MATCH") X(mtx, "NLK_MTX") X(mty, "NLK_MTY")    \
   X(match_wg8, "NLK_MATCH_WG8") X(match_bx2, "NLK_MATCH_BX2") X(match_block, "NLK_MATCH_BLOCK")              \
-  X(match_noblock, "NLK_MATCH_NOBLOCK") X(match_order, "NLK_MATCH_ORDER") X(commit_wave, "NLK_COMMIT_WAVE") X(commit_lds, "NLK_COMMIT_LDS")    \
+  X(match_noblock, "NLK_MATCH_NOBLOCK") X(match_order, "NLK_MATCH_ORDER") X(commit_wave, "NLK_COMMIT_WAVE")    \
   X(commit_band, "NLK_COMMIT_BAND") X(no_chase, "NLK_NO_CHASE") X(chase_test_skip0, "NLK_CHASE_TEST_SKIP0") X(bands, "NLK_BANDS") X(host_bands, "NLK_HOST_BANDS")                    \
   X(host_trace, "NLK_HOST_TRACE") X(gtx, "NLK_GTX") X(gty, "NLK_GTY") X(g8_tail, "NLK_G8_TAIL")              \
   X(g8_single, "NLK_G8_SINGLE") X(packed_lists, "NLK_PACKED_LISTS") X(tv_wg_pixels, "NLK_TV_WG_PIXELS") X(tv_unblocked, "NLK_TV_UNBLOCKED")      \
@@ -87,9 +87,10 @@ struct nlk_ctx {
   char err[512] = "";
   NlkBuf planes;                  // the planar copies of cur | prev | basic, one allocation (32-bit offsets between them: k_group8m.h)
   NlkBuf rowok, vmap, topk, tinfo, gcoords, marks, active, acc, tabs, wide;
-  NlkBuf skew;                    // mark words in replay-step order (k_marks_skew)
-  NlkBuf chase;                   // in-launch mask replay: [0] the generation counter, from word 64 on the tagged decision
-                                  // words (zeroed when allocated)
+  NlkBuf skew;                    // the mask replay's scratch (tu_commit.hip): the row replay's bit planes, decision bits and
+                                  // row states, or the diagonal replay's mark words in step order (k_marks_skew)
+  NlkBuf chase;                   // in-launch mask replay: the generation counter and the tagged decision words (zeroed when
+                                  // allocated; where each sits: tu_commit.hip)
   NlkBuf ms;                      // whole-image DCT: temporary image + the two basis matrices
   NlkBuf lz3;                     // Lanczos-3 recompose step: down(yh)
   void* lz3_old[16] = {};         // ... its outgrown allocations, freed with the context (a free would synchronise the
@@ -226,3 +227,22 @@ NlkGroupLauncher nlk_launch_group_generic, nlk_launch_group_any;
 int nlk_launch_match(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const NlkTile& tl, size_t lds, const float* img,
                      int maxm, bool wide);
 int nlk_launch_match_generic(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float* img);
+// tu_commit.hip: the replay of the processed mask (k_commit.h) over the mark words of the grid rows
+// [first, first + nrows); `marks` / `active` = whole-grid arrays, the decisions of the rows before `first` are final in
+// `active`; `total` = rows of the whole grid when it is replayed band by band (first > 0 continues the band before).
+// The stream is an argument: the replay works on whole-grid arrays, not on a view's records.
+// Reach 0: every target is active; 1..3: the row replay on bit planes, or the diagonal one (grids wider than 2048
+// targets, NLK_COMMIT_WAVE, NLK_COMMIT_BAND); above 3: whole grids only, from the coordinate lists of the context's
+// own match phase
+int nlk_launch_commit(nlk_ctx* c, hipStream_t stream, const uint64_t* marks, uint8_t* active, int ngx, int first,
+                      int nrows, int R, int total = 0);
+// ... its scratch for a grid of ngy rows replayed in `nbands` calls, reserved before the first: none of them grows it
+// then (growing it between two bands would synchronise the device under the bands in flight)
+int nlk_commit_reserve(nlk_ctx* c, int ngx, int R, int ngy, int nbands);
+// ... the replay a group launch runs itself: bit planes of the grid rows [0, rows) + a fresh generation of tagged words
+// (the counter lives on the device and is advanced by the bit-plane kernel: a step captured into a HIP graph gets a new
+// generation at every replay); `chase` = what the launch, whose first row is grid row row0, is given
+int nlk_chase_prepare(nlk_ctx* c, hipStream_t stream, const uint64_t* marks, int ngx, int row0, int rows, int R,
+                      NlkChase* chase);
+// ... and the byte per target of the grid rows [0, ngy) from the tagged words it left
+int nlk_launch_active_tagged(nlk_ctx* c, hipStream_t stream, uint8_t* active, int ngx, int ngy);
