@@ -44,6 +44,7 @@ HIP_SYMBOLS = [
     "nlk_yuv_format_from_tag", "nlk_yuv_frame_bytes", "nlk_dev_yuv_to_rgb", "nlk_dev_rgb_to_yuv",
     "nlk_dev_flow_invert", "nlk_bmflow_default_params", "nlk_dev_bm_flow",
     "nlk_dev_probe_add", "nlk_dev_sure_terms", "nlk_sure_mse",
+    "nlk_frame_grid", "nlk_strip_plan",
 ]
 API_SYMBOLS = [
     "rgb2opp", "opp2rgb", "warp_bicubic", "nlkalman_default_params",
@@ -75,6 +76,19 @@ class Params(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FrameGrid(C.Structure):
+    """struct nlk_frame_grid (include/nlk_hip.h): the patch grid of a frame call."""
+    _fields_ = [(k, C.c_int) for k in ("psz", "step", "ngx", "ngy", "halo", "reach")]
+
+
+class StripPlan(C.Structure):
+    """struct nlk_strip_plan (include/nlk_hip.h): grid rows, pixel rows held and pixel rows owned of one strip."""
+    _fields_ = [(k, C.c_int) for k in ("gy0", "gy1", "Y0", "Y1", "own0", "own1")]
+
+
+STRIPS_FEW_ROWS, STRIPS_THIN = 1, 2
 
 
 class SigmaParams(C.Structure):
@@ -237,6 +251,8 @@ def hip():
         L.nlk_dev_yuv_to_rgb.argtypes = [vp, fp, vp, i, i, C.POINTER(YuvFormat)]
         L.nlk_dev_rgb_to_yuv.argtypes = [vp, vp, fp, i, i, C.POINTER(YuvFormat)]
         L.nlk_host_tables.argtypes = [i, vp, vp, vp]
+        L.nlk_frame_grid.argtypes = [i, i, C.POINTER(Params), i, i, C.POINTER(FrameGrid)]
+        L.nlk_strip_plan.argtypes = [i, C.POINTER(FrameGrid), i, C.POINTER(StripPlan)]
         L.nlk_ctx_set_deterministic.argtypes = [vp, i]
         L.nlk_ctx_reload_switches.argtypes = [vp]
         L.nlk_ctx_last_group_shape.argtypes = [vp, C.POINTER(i)]
@@ -392,6 +408,25 @@ def nlf_build(bins, lo=0.0, hi=256.0, rho=NLF_RHO):
     if rc:
         raise ValueError(f"nlf_build: refused (rc={rc}): ch = {b.shape[0]}, nbins = {b.shape[1]}, lo = {lo}, hi = {hi}, rho = {rho}")
     return t
+
+
+def frame_grid(w, h, params, smoother=False, have_prev=False):
+    """nlk_frame_grid: the FrameGrid of a w x h frame call; host-only. ValueError where no patch grid exists."""
+    g = FrameGrid()
+    if hip().nlk_frame_grid(int(w), int(h), C.byref(params), int(smoother), int(have_prev), C.byref(g)):
+        raise ValueError(f"frame_grid: patch size {params.patch_sz} on a {w}x{h} frame")
+    return g
+
+
+def strip_plan(h, grid, world):
+    """nlk_strip_plan: the strips of an h-row frame with this FrameGrid, one dict(gy0, gy1, Y0, Y1, own0, own1) per
+    rank like strips.strip_plan; host-only. ValueError, whose args[1] is STRIPS_FEW_ROWS or STRIPS_THIN, where the
+    frame cannot be split."""
+    plan = (StripPlan * world)()
+    rc = hip().nlk_strip_plan(int(h), C.byref(grid), int(world), plan)
+    if rc:
+        raise ValueError(f"strip_plan: {grid.ngy} grid rows, halo {grid.halo}, {world} ranks (rc={rc})", rc)
+    return [{k: getattr(q, k) for k, _ in StripPlan._fields_} for q in plan]
 
 
 def sure_mse(R, D, n, sigma, eps):

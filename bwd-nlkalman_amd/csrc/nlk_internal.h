@@ -1,5 +1,5 @@
 // nlk_internal.h — what the translation units of libnlk_hip.so share: the context, error helpers,
-// scratch-buffer growth and the launchers each unit exports to nlk_hip.hip. (The library is built
+// scratch-buffer growth and the launchers each unit exports to the frame pipeline (tu_frame.hip). (The library is built
 // from several .hip files so that `make -j` compiles the big kernels in parallel.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -246,3 +246,10 @@ int nlk_chase_prepare(nlk_ctx* c, hipStream_t stream, const uint64_t* marks, int
                       NlkChase* chase);
 // ... and the byte per target of the grid rows [0, ngy) from the tagged words it left
 int nlk_launch_active_tagged(nlk_ctx* c, hipStream_t stream, uint8_t* active, int ngx, int ngy);
+
+// ---- nlk_hip.hip, for the frame pipeline (tu_frame.hip)
+// the opening check of every call on images: context, pointers, sizes
+int check_images(nlk_ctx* c, const void* out, const void* cur, int w, int h, int ch);
+// the orthonormal DCT-II basis [n][n] and the aggregation window [psz][psz] a frame call uploads (nlk_host_tables)
+void host_basis(float* C, int n);
+void host_window(float* W, int psz);

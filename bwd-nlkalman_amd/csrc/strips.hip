@@ -2,7 +2,8 @@
 // halo rows and the accumulator halos between neighbours, the mark words of every strip to every strip
 // (nlk_strips_* of include/nlk_hip.h). Reference analogue: the static row split of the OpenMP loop,
 // src/nlkalman.c:586 - with the processed-mask replayed over the WHOLE grid on every rank, so that the result
-// is the serial order's for any number of strips.
+// is the serial order's for any number of strips. The grid and the strips of a world are nlk_frame_grid and
+// nlk_strip_plan (host/frame_grid.c), as for host/multidev.c.
 //
 // Two transports behind one step:
 //   * RCCL (one process per GPU, one strip per process): grouped ncclSend / ncclRecv between neighbours over
@@ -24,9 +25,7 @@
 
 namespace {
 
-struct StripPlan {
-  int gy0, gy1, Y0, Y1, own0, own1;
-};
+typedef struct nlk_strip_plan StripPlan;  // (nlk_strip_plan() of host/frame_grid.c makes it)
 
 struct Rccl {
   void* lib = nullptr;
@@ -365,33 +364,23 @@ int nlk_strips_create(nlk_strips** out, int nlocal, const int* devices, int rank
   *out = nullptr;
   if (world < 1 || nlocal < 1 || rank0 < 0 || rank0 + nlocal > world || !(nlocal == 1 || nlocal == world))
     return fail(nullptr, NLK_EINVAL, "strips: %d local of %d from rank %d (one strip per process, or all of them in one)", nlocal, world, rank0);
-  const int psz = P->patch_sz, step = psz / 2;
-  if (psz < 2 || w < psz || h < psz) return fail(nullptr, NLK_EINVAL, "strips: patch size %d on a %dx%d frame", psz, w, h);
+  struct nlk_frame_grid fg;
+  if (nlk_frame_grid(w, h, P, smoother, have_prev, &fg))
+    return fail(nullptr, NLK_EINVAL, "strips: patch size %d on a %dx%d frame", P->patch_sz, w, h);
+  const int psz = fg.psz, step = fg.step;
   nlk_strips* S = new nlk_strips();
   S->world = world; S->nlocal = nlocal; S->rank0 = rank0;
   S->w = w; S->h = h; S->ch = ch; S->psz = psz; S->step = step; S->sigma = sigma; S->P = *P; S->smoother = smoother;
   S->have_prev = have_prev != 0;
-  S->halo = smoother ? P->search_sz_t : (P->search_sz_x > P->search_sz_t ? P->search_sz_x : P->search_sz_t);
-  S->ngx = (w - psz) / step + 1;
-  S->ngy = (h - psz) / step + 1;
-  const int reach = ((smoother || have_prev) ? P->search_sz_t : P->search_sz_x) / step;
+  S->halo = fg.halo; S->ngx = fg.ngx; S->ngy = fg.ngy;
   auto bail = [&](int code, const char* msg) { snprintf(nlk_g_err, sizeof nlk_g_err, "%s", msg); nlk_strips_destroy(S); return code; };
-  if (reach > 3) return bail(NLK_EUNSUP, "strips: a group reaches more than 3 grid cells (64-bit mark words cannot describe it)");
-  if (S->ngy < world) return bail(NLK_EINVAL, "strips: fewer patch-grid rows than ranks");
-  // the plan of bwd-nlkalman_amd/strips.py: rows of the patch grid, pixel rows incl. the search halo, own rows
+  if (fg.reach > 3) return bail(NLK_EUNSUP, "strips: a group reaches more than 3 grid cells (64-bit mark words cannot describe it)");
+  // rows of the patch grid, pixel rows incl. the search halo, own rows of every rank
   S->plan.resize(world);
-  for (int r = 0; r < world; ++r) {
-    StripPlan& q = S->plan[r];
-    q.gy0 = (int)((long)S->ngy * r / world);
-    q.gy1 = (int)((long)S->ngy * (r + 1) / world);
-    q.Y0 = q.gy0 * step - S->halo > 0 ? q.gy0 * step - S->halo : 0;
-    q.Y1 = (q.gy1 - 1) * step + S->halo + psz < h ? (q.gy1 - 1) * step + S->halo + psz : h;
-    q.own0 = r > 0 ? q.gy0 * step : 0;
-    q.own1 = r < world - 1 ? q.gy1 * step : h;
+  switch (nlk_strip_plan(h, &fg, world, S->plan.data())) {
+    case NLK_STRIPS_FEW_ROWS: return bail(NLK_EINVAL, "strips: fewer patch-grid rows than ranks");
+    case NLK_STRIPS_THIN: return bail(NLK_EINVAL, "strips thinner than the search halo: use fewer ranks");
   }
-  for (int r = 0; r + 1 < world; ++r)
-    if (S->plan[r].Y1 > S->plan[r + 1].own1 || S->plan[r + 1].Y0 < S->plan[r].own0)
-      return bail(NLK_EINVAL, "strips thinner than the search halo: use fewer ranks");
   S->s.resize(nlocal);
   for (int i = 0; i < nlocal; ++i) {
     Strip& T = S->s[i];

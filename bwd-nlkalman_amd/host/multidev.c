@@ -2,8 +2,9 @@
  *
  * NLK_DEVICES=0,1,2,... (a comma-separated list of HIP device indices; an index may repeat, which is
  * how the one-GPU test box exercises this path) makes nlkalman_filter_frame / nlkalman_smooth_frame
- * cut the frame into row strips of the patch grid, one per listed device, exactly like the
- * torch.distributed driver (bwd-nlkalman_amd/strips.py) does over RCCL, with one host thread per
+ * cut the frame into row strips of the patch grid, one per listed device (nlk_frame_grid and nlk_strip_plan of
+ * host/frame_grid.c: the grid and the strips of csrc/strips.hip and of the torch.distributed driver,
+ * bwd-nlkalman_amd/strips.py, which works over RCCL), with one host thread per
  * device (the devices upload, match, filter and download side by side; three barriers per call):
  *   1. every device gets its strip + search halo of the caller's host images (the previous-frame
  *      halo needs no exchange here: the whole previous frame is in host memory);
@@ -31,10 +32,10 @@ typedef struct { void *p; size_t cap; } buf_t;
 typedef struct {
   nlk_ctx *c;
   buf_t cur, prev, basic, out, acc, marks, marks_full, active, rtop, rbot;
-  int gy0, gy1, Y0, Y1, own0, own1;
 } mdev_t;
 
 static mdev_t g_dev[NLK_MAXDEV];
+static struct nlk_strip_plan g_plan[NLK_MAXDEV]; /* the strips of the call under way (nlk_strip_plan) */
 static int g_ids[NLK_MAXDEV];
 static int g_ndev = -1; /* -1: NLK_DEVICES not looked at yet */
 static int g_nlisted = 0;
@@ -154,9 +155,6 @@ static void *grow(mdev_t *D, buf_t *b, size_t bytes) {
   return b->p;
 }
 
-static int imin(int a, int b) { return a < b ? a : b; }
-static int imax(int a, int b) { return a > b ? a : b; }
-
 /* device-to-device copy ordered behind everything enqueued on the source's stream (the event it
  * records lives in the SOURCE context and several devices may pull from one source: one at a time) */
 static void pull(mdev_t *D, void *dst, mdev_t *S, const void *src, size_t n, const char *what) {
@@ -172,13 +170,14 @@ static void run_device(int d) {
   const job_t *J = &g_job;
   const int n = J->n, w = J->w, h = J->h, ch = J->ch, smoother = J->smoother;
   const struct nlkalman_params *P = J->P;
-  const int psz = P->patch_sz, step = psz / 2;
-  const int ngx = (w - psz) / step + 1, ngy = (h - psz) / step + 1;
+  struct nlk_frame_grid fg;
+  (void)nlk_frame_grid(w, h, P, smoother, J->prev != NULL, &fg); /* (nlk_multi_frame has seen it succeed) */
+  const int step = fg.step, ngx = fg.ngx, ngy = fg.ngy;
   const size_t row = (size_t)w * ch * sizeof(float), nmark = (size_t)ngx * ngy;
   mdev_t *D = &g_dev[d];
+  const struct nlk_strip_plan *Q = &g_plan[d]; /* mine; Q[-1] / Q[1]: the neighbour's above / below */
   const int on = d < n;
-  const int hl = on ? D->Y1 - D->Y0 : 0;
-  (void)h;
+  const int hl = on ? Q->Y1 - Q->Y0 : 0;
   /* 1 + 2a: upload, match */
   if (on) {
     float *dc = (float *)grow(D, &D->cur, row * hl);
@@ -186,16 +185,16 @@ static void run_device(int d) {
     float *db = J->basic ? (float *)grow(D, &D->basic, row * hl) : NULL;
     grow(D, &D->out, row * hl);
     grow(D, &D->acc, (size_t)(ch + 1) * hl * w * sizeof(float));
-    grow(D, &D->marks, (size_t)(D->gy1 - D->gy0) * ngx * 8);
+    grow(D, &D->marks, (size_t)(Q->gy1 - Q->gy0) * ngx * 8);
     grow(D, &D->marks_full, nmark * 8);
     grow(D, &D->active, nmark);
-    if (d > 0) grow(D, &D->rtop, (size_t)(ch + 1) * (g_dev[d - 1].Y1 - g_dev[d - 1].own1) * w * sizeof(float));
-    if (d + 1 < n) grow(D, &D->rbot, (size_t)(ch + 1) * (g_dev[d + 1].own0 - g_dev[d + 1].Y0) * w * sizeof(float));
-    if (nlk_h2d(D->c, dc, J->cur + (size_t)D->Y0 * w * ch, row * hl) ||
-        (J->prev && nlk_h2d(D->c, dp, J->prev + (size_t)D->Y0 * w * ch, row * hl)) ||
-        (J->basic && nlk_h2d(D->c, db, J->basic + (size_t)D->Y0 * w * ch, row * hl)))
+    if (d > 0) grow(D, &D->rtop, (size_t)(ch + 1) * (Q[-1].Y1 - Q[-1].own1) * w * sizeof(float));
+    if (d + 1 < n) grow(D, &D->rbot, (size_t)(ch + 1) * (Q[1].own0 - Q[1].Y0) * w * sizeof(float));
+    if (nlk_h2d(D->c, dc, J->cur + (size_t)Q->Y0 * w * ch, row * hl) ||
+        (J->prev && nlk_h2d(D->c, dp, J->prev + (size_t)Q->Y0 * w * ch, row * hl)) ||
+        (J->basic && nlk_h2d(D->c, db, J->basic + (size_t)Q->Y0 * w * ch, row * hl)))
       md_die("upload", D->c);
-    if (nlk_dev_strip_match(D->c, dc, dp, db, w, hl, ch, J->sigma, P, D->gy0 * step - D->Y0, D->gy1 - D->gy0, smoother,
+    if (nlk_dev_strip_match(D->c, dc, dp, db, w, hl, ch, J->sigma, P, Q->gy0 * step - Q->Y0, Q->gy1 - Q->gy0, smoother,
                             D->marks.p, &g_reach[d]))
       md_die("strip_match", D->c);
   }
@@ -207,11 +206,11 @@ static void run_device(int d) {
   /* 2b: the mark words of every strip, device to device; whole-grid replay on each; 3: the strip's groups */
   if (on) {
     for (int e = 0; e < n; ++e)
-      pull(D, (unsigned long long *)D->marks_full.p + (size_t)g_dev[e].gy0 * ngx, &g_dev[e], g_dev[e].marks.p,
-           (size_t)(g_dev[e].gy1 - g_dev[e].gy0) * ngx * 8, "mark words");
+      pull(D, (unsigned long long *)D->marks_full.p + (size_t)g_plan[e].gy0 * ngx, &g_dev[e], g_dev[e].marks.p,
+           (size_t)(g_plan[e].gy1 - g_plan[e].gy0) * ngx * 8, "mark words");
     if (nlk_dev_mask_commit(D->c, D->marks_full.p, ngx, ngy, g_reach[d], (unsigned char *)D->active.p) ||
         nlk_dev_zero(D->c, D->acc.p, (size_t)(ch + 1) * hl * w * sizeof(float)) ||
-        nlk_dev_strip_group(D->c, (float *)D->acc.p, (unsigned char *)D->active.p + (size_t)D->gy0 * ngx))
+        nlk_dev_strip_group(D->c, (float *)D->acc.p, (unsigned char *)D->active.p + (size_t)Q->gy0 * ngx))
       md_die("mask_commit / strip_group", D->c);
   }
   pthread_barrier_wait(&g_bar);
@@ -219,37 +218,37 @@ static void run_device(int d) {
   if (on) {
     if (d > 0) { /* rows [own1(d-1), Y1(d-1)) of device d-1 = my first own rows */
       mdev_t *U = &g_dev[d - 1];
-      const int nr = U->Y1 - U->own1, hu = U->Y1 - U->Y0;
+      const int nr = Q[-1].Y1 - Q[-1].own1, hu = Q[-1].Y1 - Q[-1].Y0;
       for (int p = 0; p <= ch; ++p)
-        pull(D, (float *)D->rtop.p + (size_t)p * nr * w, U, (float *)U->acc.p + ((size_t)p * hu + (U->own1 - U->Y0)) * w,
+        pull(D, (float *)D->rtop.p + (size_t)p * nr * w, U, (float *)U->acc.p + ((size_t)p * hu + (Q[-1].own1 - Q[-1].Y0)) * w,
              (size_t)nr * w * sizeof(float), "halo copy");
     }
     if (d + 1 < n) { /* rows [Y0(d+1), own0(d+1)) of device d+1 = my last own rows */
       mdev_t *L = &g_dev[d + 1];
-      const int nr = L->own0 - L->Y0, hb = L->Y1 - L->Y0;
+      const int nr = Q[1].own0 - Q[1].Y0, hb = Q[1].Y1 - Q[1].Y0;
       for (int p = 0; p <= ch; ++p)
         pull(D, (float *)D->rbot.p + (size_t)p * nr * w, L, (float *)L->acc.p + (size_t)p * hb * w,
              (size_t)nr * w * sizeof(float), "halo copy");
     }
     if (d > 0) {
-      const int nr = g_dev[d - 1].Y1 - g_dev[d - 1].own1;
+      const int nr = Q[-1].Y1 - Q[-1].own1;
       for (int p = 0; p <= ch; ++p)
-        if (nlk_dev_add(D->c, (float *)D->acc.p + ((size_t)p * hl + (D->own0 - D->Y0)) * w,
+        if (nlk_dev_add(D->c, (float *)D->acc.p + ((size_t)p * hl + (Q->own0 - Q->Y0)) * w,
                         (float *)D->rtop.p + (size_t)p * nr * w, (size_t)nr * w))
           md_die("halo add", D->c);
     }
     if (d + 1 < n) {
-      const int nr = g_dev[d + 1].own0 - g_dev[d + 1].Y0;
+      const int nr = Q[1].own0 - Q[1].Y0;
       for (int p = 0; p <= ch; ++p)
-        if (nlk_dev_add(D->c, (float *)D->acc.p + ((size_t)p * hl + (g_dev[d + 1].Y0 - D->Y0)) * w,
+        if (nlk_dev_add(D->c, (float *)D->acc.p + ((size_t)p * hl + (Q[1].Y0 - Q->Y0)) * w,
                         (float *)D->rbot.p + (size_t)p * nr * w, (size_t)nr * w))
           md_die("halo add", D->c);
     }
     /* 5: own rows */
     if (nlk_dev_frame_normalize(D->c, (float *)D->out.p, (float *)D->acc.p, (float *)D->cur.p, w, hl, ch,
-                                D->own0 - D->Y0, D->own1 - D->Y0) ||
-        nlk_d2h(D->c, J->out + (size_t)D->own0 * w * ch, (float *)D->out.p + (size_t)(D->own0 - D->Y0) * w * ch,
-                row * (D->own1 - D->own0)))
+                                Q->own0 - Q->Y0, Q->own1 - Q->Y0) ||
+        nlk_d2h(D->c, J->out + (size_t)Q->own0 * w * ch, (float *)D->out.p + (size_t)(Q->own0 - Q->Y0) * w * ch,
+                row * (Q->own1 - Q->own0)))
       md_die("normalize / download", D->c);
   }
   /* (nobody reuses a buffer a neighbour may still be pulling from before every device is done) */
@@ -262,30 +261,11 @@ static void run_device(int d) {
 int nlk_multi_frame(int smoother, float *out, const float *cur, const float *prev, const float *basic, int w, int h,
                     int ch, float sigma, const struct nlkalman_params *P) {
   static int told = 0;
-  const int psz = P->patch_sz, step = psz / 2;
-  if (psz < 2 || w < psz || h < psz) return 0; /* (the single-device path reports it) */
-  const int ngy = (h - psz) / step + 1;
-  const int halo = smoother ? P->search_sz_t : imax(P->search_sz_x, P->search_sz_t);
-  const int wmark = (smoother || prev) ? P->search_sz_t : P->search_sz_x;
-  int n = g_ndev;
-  for (; n > 1; --n) {
-    if (ngy / n < 1) continue;
-    /* strips (the plan of strips.py): rows of the patch grid, pixel rows incl. the search halo, own rows */
-    for (int d = 0; d < n; ++d) {
-      mdev_t *D = &g_dev[d];
-      D->gy0 = (int)((long)ngy * d / n);
-      D->gy1 = (int)((long)ngy * (d + 1) / n);
-      D->Y0 = imax(0, D->gy0 * step - halo);
-      D->Y1 = imin(h, (D->gy1 - 1) * step + halo + psz);
-      D->own0 = d > 0 ? D->gy0 * step : 0;
-      D->own1 = d < n - 1 ? D->gy1 * step : h;
-    }
-    int thin = 0; /* a strip may only spill into its direct neighbour's own rows */
-    for (int d = 0; d + 1 < n; ++d)
-      if (g_dev[d].Y1 > g_dev[d + 1].own1 || g_dev[d + 1].Y0 < g_dev[d].own0) thin = 1;
-    if (!thin) break;
-  }
-  if (n < 2 || wmark / step > 3) {
+  struct nlk_frame_grid fg;
+  if (nlk_frame_grid(w, h, P, smoother, prev != NULL, &fg)) return 0; /* (the single-device path reports it) */
+  int n = g_ndev; /* as many of the listed devices as the strips are not too thin for */
+  while (n > 1 && nlk_strip_plan(h, &fg, n, g_plan) != NLK_OK) --n;
+  if (n < 2 || fg.reach > 3) {
     if (!told)
       fprintf(stderr, "nlkalman (hip): NLK_DEVICES: this call is not split (%s); it runs on one device\n",
               n < 2 ? "strips thinner than the search halo" : "group reach above 3 grid cells");

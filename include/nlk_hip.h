@@ -589,6 +589,25 @@ int nlk_ctx_read_records(nlk_ctx *ctx, int *ngrid, int *kmax, int *gmax,
                          unsigned char *active, int *nsel, int *np0, int *nagg,
                          unsigned int *topk, unsigned int *gcoords);
 
+/* ---- The patch grid of a frame call and its split into row strips (host only, plain C: host/frame_grid.c links by
+ * itself). THE statement of both for the frame calls, csrc/strips.hip and host/multidev.c.
+ *   step   patch_sz / 2: targets sit at (i * step, j * step), i < ngx, j < ngy
+ *   halo   pixel rows any search window or group of the call reaches beyond its target's: search_sz_t for the
+ *          smoother, else the larger of the two radii (with or without a previous frame)
+ *   reach  grid cells the groups that mark the processed mask reach: the temporal radius for the smoother and for a
+ *          frame with a previous frame, else the spatial one, over step (src/nlkalman.c:637, :931)
+ * Returns NLK_EINVAL and writes nothing when patch_sz < 2 or the image is smaller than a patch. */
+struct nlk_frame_grid { int psz, step, ngx, ngy, halo, reach; };
+int nlk_frame_grid(int w, int h, const struct nlkalman_params *prms, int smoother, int have_prev,
+                   struct nlk_frame_grid *out);
+/* The grid rows of an h-row frame cut into `world` strips: plan[r] = grid rows [gy0, gy1), the pixel rows [Y0, Y1) the
+ * strip holds (its targets' patches and the halo around them) and the pixel rows [own0, own1) it owns (normalises and
+ * returns). NLK_STRIPS_FEW_ROWS (nothing written): fewer grid rows than strips; NLK_STRIPS_THIN: a strip would spill
+ * beyond its direct neighbour's own rows, i.e. the strips are thinner than the halo. */
+struct nlk_strip_plan { int gy0, gy1, Y0, Y1, own0, own1; };
+enum { NLK_STRIPS_FEW_ROWS = 1, NLK_STRIPS_THIN = 2 };
+int nlk_strip_plan(int h, const struct nlk_frame_grid *grid, int world, struct nlk_strip_plan *plan);
+
 /* ---- One frame over several GPUs, driven from C (csrc/strips.hip; the reference's analogue is
  * the static row split of its OpenMP loop, src/nlkalman.c:586). The patch-grid rows are cut into `world` strips.
  * Per step and strip: the previous frame's halo rows come from the neighbours, the strip is matched (its interior

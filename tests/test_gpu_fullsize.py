@@ -194,6 +194,30 @@ def test_host_pointer_calls_pipeline_the_frame_in_row_bands(ctx, built, synth, m
             _same(built.smooth_frame(d0, d2, None, sigma, ps), ds, d0, f"{tag}: smo1")
 
 
+def test_host_pointer_calls_form_two_bands_on_the_smallest_frame(ctx, built, synth, monkeypatch, capfd):
+    """The row bands of the host-pointer calls at the smallest size that still forms two: 64 x 168 RGB has 41 grid rows,
+    and a band needs 4 * (reach + 1) + 8 of them: 20 for the first frame (reach 2), 16 for the temporal one (reach 1).
+    The previous frame has the warp's NaN ring and a hole across the seam between the bands (band 0 reads pixel rows up
+    to 84 + the search radius, band 1's targets start at row 80). Each call equals the device call up to the order of
+    the accumulator's adds, and its trace says that two bands ran: the single-upload path cannot pass."""
+    w, h, ch, sigma = 64, 168, 3, 20.0
+    n0, n1, _ = synth.noisy_pair(w, h, ch, sigma, 1)
+    o0, o1 = built.rgb2opp(n0), built.rgb2opp(n1)
+    p1 = built.default_params(sigma, built.FLT1)
+    d0, _ = _dev_frame(ctx, False, o0, None, None, sigma, p1)
+    hole = d0.copy()
+    hole[:1], hole[-2:], hole[:, :1], hole[:, -2:] = np.nan, np.nan, np.nan, np.nan   # the warp's NaN ring
+    hole[76:91, 20:44] = np.nan
+    d1, _ = _dev_frame(ctx, False, o1, hole, None, sigma, p1)
+    monkeypatch.setenv("NLK_HOST_BANDS", "2")
+    monkeypatch.setenv("NLK_HOST_TRACE", "1")
+    for what, cur, prev, want in (("flt1 spatial", o0, None, d0), ("flt1 temporal", o1, hole, d1)):
+        capfd.readouterr()
+        got = built.filter_frame(cur, prev, None, sigma, p1)
+        assert "2 bands" in capfd.readouterr().err, f"host bands 2, 64 x 168: {what}: not the banded pipeline"
+        _same(got, want, cur, f"host bands 2, 64 x 168: {what}")
+
+
 @pytest.mark.parametrize("seed", [3, 4, 5])
 def test_host_pointer_pipeline_on_odd_sizes(ctx, built, synth, seed):
     """Row bands of the host-pointer calls on frames whose sizes are nothing round: one or three channels,
