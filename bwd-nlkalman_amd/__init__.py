@@ -41,6 +41,7 @@ HIP_SYMBOLS = [
     "nlk_curve_default_params", "nlk_dev_estimate_noise_curve", "nlk_vst_scale", "nlk_dev_vst_forward",
     "nlk_dev_vst_inverse", "nlk_dev_noise_affine",
     "nlk_nlf_build", "nlk_dev_nlf_forward", "nlk_dev_nlf_inverse", "nlk_dev_despike",
+    "nlk_dev_defect_step", "nlk_defect_schedule",
     "nlk_yuv_format_from_tag", "nlk_yuv_frame_bytes", "nlk_dev_yuv_to_rgb", "nlk_dev_rgb_to_yuv",
     "nlk_dev_flow_invert", "nlk_bmflow_default_params", "nlk_dev_bm_flow",
     "nlk_dev_probe_add", "nlk_dev_sure_terms", "nlk_sure_mse",
@@ -245,6 +246,8 @@ def hip():
         for fn in (L.nlk_dev_nlf_forward, L.nlk_dev_nlf_inverse):
             fn.argtypes = [vp, fp, fp, C.c_size_t, i, C.POINTER(NlfTable)]
         L.nlk_dev_despike.argtypes = [vp, fp, fp, vp, i, i, i, i, f]
+        L.nlk_dev_defect_step.argtypes = [vp, fp, fp, fp, fp, vp, vp, i, i, i, i, f, f]
+        L.nlk_defect_schedule.argtypes = [C.c_long, i, f, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.nlk_yuv_format_from_tag.argtypes = [C.POINTER(YuvFormat), C.c_char_p]
         L.nlk_yuv_frame_bytes.argtypes = [i, i, C.POINTER(YuvFormat)]
         L.nlk_yuv_frame_bytes.restype = C.c_size_t
@@ -844,6 +847,25 @@ class Context:
             return self.download(d, (ch,), np.uint32)
         finally:
             self.free(d)
+
+    # ---- a defect map learned over time (include/nlk_hip.h: nlk_dev_defect_step, nlk_defect_schedule)
+    def defect_step(self, d_out, d_in, d_mean_out, d_mean_in, w, h, ch, thr, gain, radius=1, d_map=None, d_count=None):
+        """One frame of the defect map (the rule: tests/defectmap_ref.py): where the mean d_mean_in of the frames before
+        lies more than thr outside the range of its ring, d_out = the median of d_in's ring, anything else d_in bit for
+        bit; d_mean_out = d_mean_in + (d_in - d_mean_in) * gain. d_mean_in None: the first frame (out = in, the mean
+        starts as the frame; thr and gain are not used). d_map: None, or w h ch device bytes, 1 = hit; d_count: None,
+        or ch device uint32, the replaced samples of every channel. No two of the four planes may overlap. Not
+        synchronised."""
+        self._chk(self.L.nlk_dev_defect_step(self.h, d_out, d_in, d_mean_out, d_mean_in, d_map, d_count, w, h, ch,
+                                             int(radius), float(thr), float(gain)))
+
+    @staticmethod
+    def defect_schedule(t, n_window, k_sigma):
+        """nlk_defect_schedule: (thr, gain) of the frame of index t >= 1 (float32 values as Python floats)."""
+        thr, gain = C.c_float(), C.c_float()
+        if hip().nlk_defect_schedule(int(t), int(n_window), float(k_sigma), C.byref(thr), C.byref(gain)) != 0:
+            raise ValueError(f"defect_schedule(t={t}, n_window={n_window}): want t >= 1 and n_window >= 1")
+        return thr.value, gain.value
 
     def noise_affine(self, d_out, d_in, n, ch, ab, seed):
         """d_out[i] = d_in[i] + sqrt(max(a_c d_in[i] + b_c, 0)) N_i with awgn's deviates N_i (d_out may be d_in)."""

@@ -56,14 +56,12 @@ __device__ __forceinline__ void despike_middle(float (&a)[N], float& lo, float& 
   hi = a[N / 2];
 }
 
-// one sample per lane: `p` = the lane's sample in its row (FAST) or the image (general: row offsets yo[], flat column
-// offsets xo[]); returns what goes to out, hit = it was replaced
+// the ring walk (k_defect.h walks the same way): a[] = the ring of the lane's sample, row by row, and the sample itself
+// is returned. `p` = the lane's sample in its row (FAST) or the image (general: row offsets yo[], flat column offsets
+// xo[])
 template <int R, bool FAST>
-__device__ __forceinline__ float despike_sample(const float* p, ptrdiff_t W, int ch, const ptrdiff_t* yo, const int* xo,
-                                                float thr, bool& hit) {
-#pragma clang fp contract(off)
-  constexpr int N = 8 * R;
-  float a[N];
+__device__ __forceinline__ float despike_ring(float (&a)[8 * R], const float* p, ptrdiff_t W, int ch, const ptrdiff_t* yo,
+                                              const int* xo) {
   int n = 0;
 #pragma unroll
   for (int dy = -R; dy <= R; ++dy) {
@@ -73,14 +71,31 @@ __device__ __forceinline__ float despike_sample(const float* p, ptrdiff_t W, int
       a[n++] = FAST ? p[dy * W + dx * ch] : p[yo[dy + R] + xo[dx + R]];
     }
   }
-  const float v = FAST ? p[0] : p[yo[R] + xo[R]];
-  float mn = a[0], mx = a[0], nf = __builtin_fmaf(v, 0.f, a[0] * 0.f);
+  return FAST ? p[0] : p[yo[R] + xo[R]];
+}
+
+// the ring's minimum and maximum, and nf: 0 while v and the ring are finite, NaN otherwise
+template <int N>
+__device__ __forceinline__ void despike_range(const float (&a)[N], float v, float& mn, float& mx, float& nf) {
+  mn = a[0], mx = a[0], nf = __builtin_fmaf(v, 0.f, a[0] * 0.f);
 #pragma unroll
   for (int k = 1; k < N; ++k) {
     mn = fminf(mn, a[k]);
     mx = fmaxf(mx, a[k]);
     nf = __builtin_fmaf(a[k], 0.f, nf);
   }
+}
+
+// one sample per lane (p, W, ch, yo, xo: as despike_ring's); returns what goes to out, hit = it was replaced
+template <int R, bool FAST>
+__device__ __forceinline__ float despike_sample(const float* p, ptrdiff_t W, int ch, const ptrdiff_t* yo, const int* xo,
+                                                float thr, bool& hit) {
+#pragma clang fp contract(off)
+  constexpr int N = 8 * R;
+  float a[N];
+  const float v = despike_ring<R, FAST>(a, p, W, ch, yo, xo);
+  float mn, mx, nf;
+  despike_range<N>(a, v, mn, mx, nf);
   hit = nf == 0.f && (v > mx + thr || v < mn - thr);
   float r = v;
   if (__builtin_amdgcn_ballot_w64(hit) != 0) {  // wave-uniform

@@ -41,7 +41,16 @@
  *           at the run's sigma; the first frame's measurement (auto, vst, nlf) stays on the frame as read. K = 4 is the
  *           value DESIGN.md §9's table was made with. The gt tool's noisy files and measures are not touched by it.
  *           Without the option nothing of this happens: the same launches and allocations as before.
- *   --sure  after --despike, in front of the rest, in all three tools (the scripts have no such thing): the error of every
+ *   --defect-map K[,R[,N]]  after --despike, in front of --sure, in all three tools (the scripts have no such thing): a
+ *           defect map learned over time (nlk_dev_defect_step). A sensor defect sits at the same place in
+ *           every frame, scene and noise do not: where the running mean of the noisy frames 0 .. t - 1 (window N, default
+ *           32; no motion compensation) lies more than K sigma / sqrt(min(t, N)) outside the range of its ring (radius
+ *           R = 1, the default, or 2), frame t's sample becomes the median of its own ring before the filter sees it.
+ *           Streaming: the first frame passes as it is, the sites --despike cannot see at a high sigma are flagged a
+ *           few frames later. It runs where --despike runs and in front of it when both are given. K = 4 is the value
+ *           DESIGN.md §9's table was made with; a static one-pixel detail is indistinguishable from a defect (the
+ *           table's static row). Without the option nothing of this happens: the same launches and allocations as before.
+ *   --sure  after --defect-map, in front of the rest, in all three tools (the scripts have no such thing): the error of every
  *           flt1 / flt2 frame is estimated without clean frames by Monte-Carlo SURE (seq_sure_step, host/seq_step.h;
  *           DESIGN.md §9): one more FLT1 and FLT2 per frame, on the noisy frame plus a probe of +-eps. OUT/measures-sure
  *           gets, per pass, "F1 I MSE_hat PSNR_hat R/N div" for every frame I and "F1 total ..." (finish_sure), each
@@ -464,7 +473,18 @@ int main(int argc, const char **argv) {
     argv += 2;
     argc -= 2;
   }
-  if (argc > 1 && !strcmp(argv[1], "--sure")) { /* after --despike, in front of the rest */
+  float defect_k = 0.f;
+  int defect_r = 1, defect_n = SEQ_DEFECT_N;
+  if (argc > 1 && !strcmp(argv[1], "--defect-map")) { /* after --despike, in front of --sure */
+    if (argc < 3 || seq_defect_parse(argv[2], &defect_k, &defect_r, &defect_n)) {
+      fprintf(stderr, SEQ_DEFECT_WANT, PROG, argc < 3 ? "" : argv[2]);
+      return 1;
+    }
+    argv[2] = argv[0];
+    argv += 2;
+    argc -= 2;
+  }
+  if (argc > 1 && !strcmp(argv[1], "--sure")) { /* after --defect-map, in front of the rest */
     S.on = 1;
     argv[1] = argv[0];
     ++argv;
@@ -492,6 +512,9 @@ int main(int argc, const char **argv) {
                       "  --despike K[,R] (after --of, in front of --sure): a sample more than K sigma outside its ring's range (radius\n"
                       "  R = 1 | 2) becomes the ring's median before the filter sees the frame: stuck, hot and dead pixels (K = 4: the\n"
                       "  value of DESIGN.md's table)\n"
+                      "  --defect-map K[,R[,N]] (after --despike, in front of --sure): a defect map learned over time: where the mean\n"
+                      "  of the noisy frames before (window N = 2 .. 4096, default 32) lies more than K sigma / sqrt(frames) outside\n"
+                      "  its ring's range, the frame's sample becomes its ring's median (K = 4: the value of DESIGN.md's table)\n"
                       "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
                       "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
     else if (lsmo)
@@ -500,6 +523,9 @@ int main(int argc, const char **argv) {
                       "  --despike K[,R] (after --of, in front of --sure): a sample more than K sigma outside its ring's range (radius\n"
                       "  R = 1 | 2) becomes the ring's median before the filter sees the frame: stuck, hot and dead pixels (K = 4: the\n"
                       "  value of DESIGN.md's table)\n"
+                      "  --defect-map K[,R[,N]] (after --despike, in front of --sure): a defect map learned over time: where the mean\n"
+                      "  of the noisy frames before (window N = 2 .. 4096, default 32) lies more than K sigma / sqrt(frames) outside\n"
+                      "  its ring's range, the frame's sample becomes its ring's median (K = 4: the value of DESIGN.md's table)\n"
                       "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
                       "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
     else
@@ -508,6 +534,9 @@ int main(int argc, const char **argv) {
                       "  --despike K[,R] (after --of, in front of --sure): a sample more than K sigma outside its ring's range (radius\n"
                       "  R = 1 | 2) becomes the ring's median before the filter sees the frame: stuck, hot and dead pixels (K = 4: the\n"
                       "  value of DESIGN.md's table)\n"
+                      "  --defect-map K[,R[,N]] (after --despike, in front of --sure): a defect map learned over time: where the mean\n"
+                      "  of the noisy frames before (window N = 2 .. 4096, default 32) lies more than K sigma / sqrt(frames) outside\n"
+                      "  its ring's range, the frame's sample becomes its ring's median (K = 4: the value of DESIGN.md's table)\n"
                       "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
                       "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
     return 1;
@@ -566,6 +595,7 @@ int main(int argc, const char **argv) {
   int w = 0, h = 0, ch = 0;
   size_t bytes = 0;
   struct seq_work W = {0};
+  struct seq_defects D = {0};
   float *d_rgb = NULL, *flt1 = NULL;
   float *d_lsm1 = NULL; /* lsmo: the smoothed frame (its flow and mask are W.d_fflow, W.d_focc) */
   float **flt2 = calloc(nframes, sizeof(float *));  /* kept for the backward pass */
@@ -608,6 +638,7 @@ int main(int argc, const char **argv) {
       }
       d_rgb = dev_frame(bytes);
       CHK(seq_work_alloc(C, &W, w, h, ch, lsmo && smoothing));
+      if (defect_k != 0.f) CHK(seq_defects_alloc(C, &D, defect_k, defect_r, defect_n, w, h, ch));
       if (lsmo && smoothing) d_lsm1 = dev_frame(bytes);
       if (S.on) {
         void *d = NULL;
@@ -670,6 +701,7 @@ int main(int argc, const char **argv) {
     float *n1 = dev_frame(bytes), *n2 = dev_frame(bytes);
     const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .of = of, .sig = &sig, .f1 = &f1, .f2 = &f2,
                                   .fscale = fs1, .dw = dw1, .th = th1, .work = &W,
+                                  .defects = defect_k != 0.f ? &D : NULL,
                                   .despike_k = despike_k, .despike_r = despike_r, .d_rgb = d_rgb,
                                   .prev_flt1 = t ? flt1 : NULL, .prev_flt2 = t ? flt2[t - 1] : NULL,
                                   .flt1 = n1, .flt2 = n2};

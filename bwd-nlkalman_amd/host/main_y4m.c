@@ -22,6 +22,10 @@
  *                    the filter sees it, as nlkalman-seq's --despike (nlk_dev_despike at thr = K sigma, ring radius R = 1,
  *                    the default, or 2: the 2 x 2 blob a 4:2:0 chroma impulse becomes in RGB). K = 4 is the value
  *                    DESIGN.md §9's table was made with
+ *     --defect-map K[,R[,N]]   a defect map learned over time, as nlkalman-seq's --defect-map (nlk_dev_defect_step): where
+ *                    the running mean of the frames before (window N, default 32) lies more than K sigma / sqrt(frames)
+ *                    outside its ring's range (radius R = 1 | 2), the frame's sample becomes its ring's median. Streaming:
+ *                    frame t is cleaned with the evidence of the frames 0 .. t - 1; in front of --despike when both are given
  *     --sure         the error of every flt2 frame estimated without clean frames by Monte-Carlo SURE (seq_sure_step,
  *                    host/seq_step.h): one more FLT1 and FLT2 per frame. One stderr line per frame,
  *                    "sure T MSE_hat PSNR_hat R/N div" (T from 1, each value "%.9g", PSNR at 255), and at the end
@@ -195,6 +199,8 @@ static int usage(void) {
           "  --of tvl1|bm\n"
           "  --despike K[,R]  a sample more than K sigma outside its ring's range (radius R = 1 | 2) becomes the ring's median\n"
           "          before the filter sees the frame: stuck, hot and dead pixels (K = 4: the value of DESIGN.md's table)\n"
+          "  --defect-map K[,R[,N]]  a defect map learned over time: where the mean of the frames before (window N = 2 .. 4096,\n"
+          "          default 32) lies more than K sigma / sqrt(frames) outside its ring's range, the sample becomes its ring's median\n"
           "  --sure  one stderr line per frame, \"sure T MSE_hat PSNR_hat R/N div\": flt2's error estimated without clean\n"
           "          frames (Monte-Carlo SURE; under SIG = vst | nlf in the stabilised domain, at the run's sigma)\n", PROG);
   return 1;
@@ -202,7 +208,7 @@ static int usage(void) {
 
 int main(int argc, const char **argv) {
   const char *matrix_s = "auto", *range_s = "auto", *fpm = "", *opm = "1 0.25 0.75", *pos[3] = {NULL, NULL, NULL};
-  const char *smooth_s = NULL, *spm = "", *of_s = "tvl1", *despike_s = NULL;
+  const char *smooth_s = NULL, *spm = "", *of_s = "tvl1", *despike_s = NULL, *defect_s = NULL;
   long max_frames = -1;
   int copy = 0, want_probe = 0, verbose = 0, npos = 0, want_sure = 0;
   for (int i = 1; i < argc; ++i) {
@@ -216,6 +222,7 @@ int main(int argc, const char **argv) {
     else if (!strcmp(a, "--spm")) val = &spm;
     else if (!strcmp(a, "--of")) val = &of_s;
     else if (!strcmp(a, "--despike")) val = &despike_s;
+    else if (!strcmp(a, "--defect-map")) val = &defect_s;
     if (val) {
       if (++i >= argc) { fprintf(stderr, "%s: %s needs a value\n", PROG, a); return 1; }
       *val = argv[i];
@@ -264,6 +271,12 @@ int main(int argc, const char **argv) {
   int despike_r = 1;
   if (despike_s && seq_despike_parse(despike_s, &despike_k, &despike_r)) {
     fprintf(stderr, SEQ_DESPIKE_WANT, PROG, despike_s);
+    return 1;
+  }
+  float defect_k = 0.f;
+  int defect_r = 1, defect_n = SEQ_DEFECT_N;
+  if (defect_s && seq_defect_parse(defect_s, &defect_k, &defect_r, &defect_n)) {
+    fprintf(stderr, SEQ_DEFECT_WANT, PROG, defect_s);
     return 1;
   }
   int matrix = 0, range = -1;
@@ -334,6 +347,8 @@ int main(int argc, const char **argv) {
   if (copy) smooth = SEQ_LAG1_OFF; /* (nothing is filtered) */
   struct seq_work W;
   CHK(seq_work_alloc(C, &W, w, h, ch, smooth));
+  struct seq_defects D = {0};
+  if (defect_k != 0.f && !copy) CHK(seq_defects_alloc(C, &D, defect_k, defect_r, defect_n, w, h, ch));
   /* the codes; the RGB frame, flt1 and flt2 of this frame and the previous one, by turns, --smooth: the smoothed frame */
   void *d_yuv = NULL, *fr[6] = {0};
   CHK(nlk_dev_alloc(C, &d_yuv, hd.frame_bytes));
@@ -366,6 +381,7 @@ int main(int argc, const char **argv) {
       const int cur = (int)(t & 1), prv = cur ^ 1;
       const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .of = of, .sig = &sig, .f1 = &f1, .f2 = &f2,
                                     .fscale = fs, .dw = dw, .th = th, .work = &W,
+                                    .defects = defect_k != 0.f ? &D : NULL,
                                     .despike_k = despike_k, .despike_r = despike_r, .d_rgb = d_rgb,
                                     .prev_flt1 = t ? flt1[prv] : NULL, .prev_flt2 = t ? flt2[prv] : NULL,
                                     .flt1 = flt1[cur], .flt2 = flt2[cur]};
@@ -427,6 +443,7 @@ int main(int argc, const char **argv) {
     seq_sure_free(C, &U);
     nlk_dev_free(C, d_terms);
   }
+  seq_defects_free(C, &D);
   seq_work_free(C, &W);
   return failed;
 }

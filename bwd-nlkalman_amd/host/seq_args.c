@@ -1,4 +1,4 @@
-/* seq_args.c — the grammar of the sequence tools' SIG argument and of --despike's value (seq_step.h). Plain C: nothing of the device libraries
+/* seq_args.c — the grammar of the sequence tools' SIG argument and of --despike's and --defect-map's values (seq_step.h). Plain C: nothing of the device libraries
  * is needed to link it. */
 #include <math.h>
 #include <stdio.h>
@@ -31,5 +31,31 @@ int seq_despike_parse(const char *text, float *k, int *r) {
   } else if (*end) return 1;
   *k = v;
   *r = radius;
+  return 0;
+}
+
+int seq_defect_parse(const char *text, float *k, int *r, int *n) {
+  char *end = NULL;
+  const float v = text ? strtof(text, &end) : 0.f;
+  int radius = 1, window = SEQ_DEFECT_N;
+  if (!text || end == text || !isfinite(v) || !(v > 0.f)) return 1;
+  if (*end == ',') { /* ",R": one digit, 1 or 2 */
+    if (end[1] != '1' && end[1] != '2') return 1;
+    radius = end[1] - '0';
+    end += 2;
+    if (*end == ',') { /* ",N": digits only, 2 .. 4096 */
+      const char *p = end + 1;
+      long w = 0;
+      if (!*p || *p == '0') return 1;
+      for (; *p >= '0' && *p <= '9' && w <= 4096; ++p) w = 10 * w + (*p - '0');
+      if (*p || w < 2 || w > 4096) return 1;
+      window = (int)w;
+      end = (char *)p;
+    }
+  }
+  if (*end) return 1;
+  *k = v;
+  *r = radius;
+  *n = window;
   return 0;
 }

@@ -154,6 +154,23 @@ void seq_work_free(nlk_ctx *C, struct seq_work *k) {
   memset(k, 0, sizeof *k);
 }
 
+int seq_defects_alloc(nlk_ctx *C, struct seq_defects *d, float k, int r, int n, int w, int h, int ch) {
+  memset(d, 0, sizeof *d);
+  d->k = k; d->r = r; d->n = n;
+  for (int i = 0; i < 2; ++i) {
+    void *p = NULL;
+    TRY(nlk_dev_alloc(C, &p, (size_t)w * h * ch * sizeof(float)));
+    d->d_mean[i] = (float *)p;
+  }
+  return NLK_OK;
+}
+
+void seq_defects_free(nlk_ctx *C, struct seq_defects *d) {
+  for (int i = 0; i < 2; ++i)
+    if (d->d_mean[i]) nlk_dev_free(C, d->d_mean[i]);
+  memset(d, 0, sizeof *d);
+}
+
 /* the TV-L1 parameters of a w x h flow with this finest scale and data weight (lambda) */
 static struct nlk_tvl1_params seq_flow_params(int w, int h, int fscale, float dw) {
   struct nlk_tvl1_params of;
@@ -209,6 +226,15 @@ int seq_forward_step(const struct seq_step *s) {
   if (seq_sig_vst(s->sig))
     TRY(nlk_dev_vst_forward(C, s->d_rgb, s->d_rgb, (size_t)w * h * ch, ch, s->sig->vst_ab, s->sig->vst_s));
   if (seq_sig_nlf(s->sig)) TRY(nlk_dev_nlf_forward(C, s->d_rgb, s->d_rgb, (size_t)w * h * ch, ch, &s->sig->nlf));
+  if (s->defects) { /* d_noisy = the frame without the sites the mean of the frames before flags, and d_rgb too */
+    struct seq_defects *d = s->defects;
+    float thr = 0.f, gain = 1.f;
+    if (d->t > 0) TRY(nlk_defect_schedule(d->t, d->n, d->k * sigma, &thr, &gain));
+    TRY(nlk_dev_defect_step(C, k->d_noisy, s->d_rgb, d->d_mean[(d->t + 1) & 1], d->t > 0 ? d->d_mean[d->t & 1] : NULL,
+                            NULL, NULL, w, h, ch, d->r, thr, gain));
+    TRY(nlk_d2d(C, s->d_rgb, k->d_noisy, bytes));
+    ++d->t;
+  }
   if (s->despike_k != 0.f) { /* d_noisy = the despiked frame, and d_rgb too: the flow's gray image is made of it */
     TRY(nlk_dev_despike(C, k->d_noisy, s->d_rgb, NULL, w, h, ch, s->despike_r, s->despike_k * sigma));
     TRY(nlk_d2d(C, s->d_rgb, k->d_noisy, bytes));

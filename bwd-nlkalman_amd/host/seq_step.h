@@ -91,6 +91,27 @@ int seq_of_mode(const char *name);
 int seq_despike_parse(const char *text, float *k, int *r);
 #define SEQ_DESPIKE_WANT "%s: --despike %s: want K or K,R with K > 0 and R = 1 or 2\n" /* (prog, text) */
 
+/* ---- --defect-map K[,R[,N]]: a defect map learned over time (nlk_dev_defect_step, include/nlk_hip.h).
+ * Streaming: frame t is cleaned with the evidence of the frames 0 .. t - 1, whose running mean (no motion compensation)
+ * is tested at thr = K sigma / sqrt(min(t, N)) and ring radius R (nlk_defect_schedule). The grammar, nothing else
+ * (host/seq_args.c): "K", "K,R" or "K,R,N" with K finite and > 0, R = 1 or 2 (default 1) and N = 2 .. 4096 (default
+ * 32) -> 0 and *k, *r, *n; anything else: 1, and they stay as they were (the caller prints SEQ_DEFECT_WANT under its own
+ * name). K = 4, N = 32 are the values DESIGN.md §9's table was made with. */
+#define SEQ_DEFECT_N 32
+int seq_defect_parse(const char *text, float *k, int *r, int *n);
+#define SEQ_DEFECT_WANT "%s: --defect-map %s: want K, K,R or K,R,N with K > 0, R = 1 or 2 and N = 2 .. 4096\n" /* (prog, text) */
+/* the state of a run: the two mean planes (of the frame's size; the steps swap them) and the index of the next frame */
+struct seq_defects {
+  float k;
+  int r, n;
+  long t;
+  float *d_mean[2];
+};
+/* one device allocation per plane, t = 0; returns the first failing call's code (what was allocated stays for
+ * seq_defects_free) */
+int seq_defects_alloc(nlk_ctx *ctx, struct seq_defects *d, float k, int r, int n, int w, int h, int ch);
+void seq_defects_free(nlk_ctx *ctx, struct seq_defects *d);
+
 /* ---- one step of the forward recursion */
 struct seq_step {
   nlk_ctx *ctx;
@@ -101,6 +122,7 @@ struct seq_step {
   int fscale;                /* backward flow: finest scale, data weight (lambda) and occlusion threshold */
   float dw, th;
   const struct seq_work *work;
+  struct seq_defects *defects; /* NULL: off; else the defect map of the run: the step reads and advances it */
   float despike_k;           /* 0: off; else the noisy frame is despiked at thr = despike_k * sig->sigma ... */
   int despike_r;             /* ... and this ring radius (1 or 2) */
   /* per frame: */
@@ -108,7 +130,10 @@ struct seq_step {
   const float *prev_flt1, *prev_flt2; /* the previous frame's outputs (opponent space); both NULL on the first frame */
   float *flt1, *flt2;        /* out: this frame's (opponent space) */
 };
-/* variance stabilisation, then with despike_k != 0 the defective-pixel filter (in the domain where the run's sigma
+/* variance stabilisation, then with `defects` the step of the defect map (in the domain where the run's sigma holds:
+ * nlk_dev_defect_step reads d_rgb and the mean of the frames before, writes work->d_noisy and the other mean plane, then
+ * a copy back to d_rgb; defects->t advances; with defects == NULL nothing is allocated or launched that was not
+ * before), then with despike_k != 0 the defective-pixel filter (in the domain where the run's sigma
  * holds, before rgb2opp and the flow's gray image: nlk_dev_despike into work->d_noisy, which is free at that point, and
  * a copy back to d_rgb; with despike_k == 0 nothing is launched that was not before), rgb2opp, then FLT1 and FLT2: spatial on the first frame, afterwards gray -> flow (TV-L1, or
  * under SEQ_OF_BM block matching) noisy_t -> flt2_{t-1} -> occlusion mask -> warp + FLT1 -> warp + FLT2 (scripts/nlkalman-seq.sh:39-101).

@@ -72,14 +72,24 @@ class SequenceFilter:
     despike=K | (K, R): as the tools' --despike K[,R]: every pushed frame goes through Context.despike at
     thr = K * sigma and ring radius R (1, the default, or 2) after the vst / nlf transform and before anything else
     sees it (stuck, hot and dead pixels; DESIGN.md §9, whose table was made with K = 4). The pushed frame itself is
-    not modified; sure= then treats the despiked frame as the data. None: nothing is allocated or launched for it."""
+    not modified; sure= then treats the despiked frame as the data. None: nothing is allocated or launched for it.
+    defect_map=K | (K, R) | (K, R, N): as the tools' --defect-map K[,R[,N]]: a defect map learned over time
+    (Context.defect_step at Context.defect_schedule's threshold and gain). Frame t is cleaned with the
+    evidence of the frames 0 .. t - 1: where their running mean (window N = 2 .. 4096, default 32; no motion
+    compensation) lies more than K sigma / sqrt(min(t, N)) outside its ring's range (radius R = 1, the default, or 2),
+    the frame's sample becomes the median of its own ring. After the vst / nlf transform, in front of despike= when both
+    are given. .defect_map: the device uint8 map [h][w][ch] of the last step (1 = flagged). defect_counts=True: the
+    steps also count, and .defect_counts is the samples of every channel the last step replaced ([ch] uint32), downloaded
+    when asked for (it waits for the device; the count's atomics cost what Context.despike_counts' cost, so they are on
+    request only). None: nothing is allocated or launched for it."""
 
     LAG1_INVERT_STEPS = 4   # SEQ_LAG1_INVERT_STEPS of host/seq_step.h
     SURE_EPS_REL, SURE_BLOCK, SURE_FRAME_STEP = 0.05, 16, 0xD1B54A32D192ED03   # SEQ_SURE_* of host/seq_step.h
 
     def __init__(self, ctx, w, h, ch, sigma, f1=None, f2=None, s1=None, of_lambda=0.25, of_fscale=1,
                  occ_th=0.75, keep_history=True, lag1=None, lag1_of_lambda=None, lag1_of_fscale=None,
-                 lag1_occ_th=None, of="tvl1", sure=None, sure_seed=None, sure_block=None, despike=None):
+                 lag1_occ_th=None, of="tvl1", sure=None, sure_seed=None, sure_block=None, despike=None,
+                 defect_map=None, defect_counts=False):
         pkg = _p()
         self.despike, self.d_despiked = None, None
         if despike is not None:
@@ -87,6 +97,20 @@ class SequenceFilter:
             if not (np.isfinite(float(k)) and float(k) > 0 and r in (1, 2)):
                 raise ValueError(f"SequenceFilter(despike={despike!r}): want None, K or (K, R) with K > 0 and R = 1 or 2")
             self.despike = (float(k), int(r))
+        self.defects, self.defect_map, self.d_defect = None, None, None
+        if defect_map is not None:
+            kr = tuple(defect_map) if isinstance(defect_map, (tuple, list)) else (defect_map,)
+            kr = kr + (1, 32)[len(kr) - 1:] if 1 <= len(kr) <= 3 else (0, 0, 0)
+            try:
+                ok = (np.isfinite(float(kr[0])) and float(kr[0]) > 0 and kr[1] in (1, 2)
+                      and kr[2] == int(kr[2]) and 2 <= kr[2] <= 4096)
+            except (TypeError, ValueError):   # (a value that is no number at all)
+                ok = False
+            if not ok:
+                raise ValueError(f"SequenceFilter(defect_map={defect_map!r}): want None, K, (K, R) or (K, R, N) with "
+                                 "K > 0, R = 1 or 2 and N = 2 .. 4096")
+            self.defects = (float(kr[0]), int(kr[1]), int(kr[2]))
+        self.want_defect_counts = bool(defect_counts) and self.defects is not None
         if of not in ("tvl1", "bm"):
             raise ValueError(f"SequenceFilter(of={of!r}): want 'tvl1' or 'bm'")
         self.flow_estimator = of
@@ -173,6 +197,13 @@ class SequenceFilter:
         else:
             iterations.append(c.tvl1_flow(d_flow, self.d_g0, self.d_g1, w, h, of))
 
+    @property
+    def defect_counts(self):
+        """the samples of every channel that the last step's defect map replaced ([ch] uint32); waits for the device"""
+        if self.d_defect is None or self.d_defect[3] is None:
+            raise ValueError("SequenceFilter.defect_counts: want defect_map= with defect_counts=True, and a pushed frame")
+        return self.ctx.download(self.d_defect[3], (self.ch,), np.uint32)
+
     def push(self, d_noisy_rgb):
         """Next noisy frame (device pointer, HWC RGB or gray, not modified). Afterwards
         self.flt1 / self.flt2 hold its two estimates (opponent space)."""
@@ -201,6 +232,16 @@ class SequenceFilter:
                 raise ValueError(f"SequenceFilter(sigma='auto'): the first frame gives sigma = {est}")
             self._resolve(est)
         sg = self.sigma
+        if self.defects:
+            k, r, n = self.defects
+            if self.d_defect is None:   # the cleaned frame, the two means (swapped every step), the counts
+                self.d_defect = [c.alloc(self.nbytes) for _ in range(3)] + [c.alloc(4 * ch) if self.want_defect_counts else None]
+                self.defect_map = c.alloc(w * h * ch)
+            d_out, d_count = self.d_defect[0], self.d_defect[3]
+            thr, gain = c.defect_schedule(self.t, n, float(np.float32(k) * np.float32(sg))) if self.t else (0.0, 1.0)
+            c.defect_step(d_out, d_noisy_rgb, self.d_defect[1 + (self.t + 1) % 2],
+                          self.d_defect[1 + self.t % 2] if self.t else None, w, h, ch, thr, gain, r, self.defect_map, d_count)
+            d_noisy_rgb = d_out   # what despike and the flow see
         if self.despike:
             if self.d_despiked is None:
                 self.d_despiked = c.alloc(self.nbytes)

@@ -46,6 +46,8 @@
  *   nlk_dev_yuv_to_rgb / nlk_dev_rgb_to_yuv, nlk_yuv_format_from_tag, nlk_yuv_frame_bytes
  *                                       nothing: the reference reads and writes RGB image files only
  *   nlk_dev_despike                     nothing: the reference has no counterpart (it models Gaussian noise only)
+ *   nlk_dev_defect_step, nlk_defect_schedule
+ *                                       nothing: the reference has no counterpart
  */
 #ifndef NLK_HIP_H
 #define NLK_HIP_H
@@ -475,6 +477,32 @@ int nlk_dev_nlf_inverse(nlk_ctx *ctx, float *out, const float *in, size_t n, int
  * for a row of 2^31 floats or more. */
 int nlk_dev_despike(nlk_ctx *ctx, float *out, const float *in, uint32_t *d_count, int w, int h, int ch, int radius,
                     float thr);
+
+/* ---- a defect map learned over time (the rule and the schedule are stated in float32 numpy by
+ * tests/defectmap_ref.py). A sensor defect sits at the same coordinates in every frame, scene and noise do not: the mean
+ * of the noisy frames, taken without motion compensation, carries noise sigma / sqrt(T) while the defect keeps its
+ * height, and nlk_dev_despike's range test read on that mean, at a threshold that shrinks as 1 / sqrt(T), finds what
+ * the test on one frame cannot. One call per frame, every channel of the HWC frame by itself (ring, border indices, mn,
+ * mx, lo, hi: as nlk_dev_despike's), every operation rounded by itself:
+ *   hit        mean_in > mx + thr or mean_in < mn - thr on mean_in's ring; none where mean_in or its ring is non-finite
+ *   out        at a hit (lo + hi) * 0.5f of in's ring, if in and its ring are all finite; anything else is `in`, bit for bit
+ *   mean_out   mean_in + (in - mean_in) * gain for a finite `in`, else mean_in: the raw sample at a hit too (a flagged
+ *              site that lost its evidence would flicker)
+ * mean_in == NULL is the first frame: out = in, mean_out = in (0 at a non-finite sample), no hit; thr and gain are
+ * checked and not used. The caller keeps two mean planes and swaps them. d_map: NULL, or w * h * ch bytes, every one
+ * written: 1 = hit. d_count: NULL, or ch device words: the call zeroes them and adds the replaced samples of every
+ * channel with integer atomics (the same bits on every call, like the planes). Asynchronous on the context's stream.
+ * NLK_EINVAL for what nlk_dev_despike refuses (mean_out as out), a gain outside (0, 1], and any overlap among out, in,
+ * mean_out and mean_in (the stencil reads the neighbours of both inputs): nothing is written and the context keeps
+ * working. NLK_EUNSUP for a row of 2^31 floats or more. */
+int nlk_dev_defect_step(nlk_ctx *ctx, float *out, const float *in, float *mean_out, const float *mean_in,
+                        uint8_t *d_map, uint32_t *d_count, int w, int h, int ch, int radius, float thr, float gain);
+/* the threshold and gain of the frame of index t >= 1 (the first frame, t = 0, needs neither) for a window of n_window
+ * frames and k_sigma = K * sigma: gain = 1f / (float)min(t + 1, N), thr = k_sigma * sqrtf(1f / (float)min(t, N)): an
+ * exact mean up to N frames, then an exponential window, whose noise is below sigma / sqrt(N), so that the threshold
+ * stays on the safe side. Host only, plain C (host/defect_schedule.c). NLK_EINVAL for t < 1, n_window < 1 or a NULL
+ * pointer. */
+int nlk_defect_schedule(long t, int n_window, float k_sigma, float *thr, float *gain);
 
 /* nlk_dev_awgn with a deviation that follows the signal: out[i] = (float)((double)in[i] + sqrt(max(a_c in[i] + b_c,
  * 0)) g_i), c = i mod ch, g_i exactly the normal deviate nlk_dev_awgn draws for that index and seed; ab as above
