@@ -63,7 +63,9 @@
  * scripts/nlkalman-seq.sh:30-150) happens here through the device C-ABI: per frame
  * tvl1flow(noisy_t -> flt2_{t-1}) -> occlusion mask -> warp + FLT1 -> warp + FLT2, then
  * backwards tvl1flow(flt2_t -> smo1_{t+1}) -> mask -> warp + SMO1: seq_forward_step, then seq_lag1_step against
- * smo1_{t+1} in its TV-L1 mode, on the work images of one struct seq_work (host/seq_step.h). Frames stay in the
+ * smo1_{t+1} in its TV-L1 mode, on one struct seq_run (host/seq_step.h): the options below (read by seq_opts_read,
+ * which nlkalman-y4m calls too), SIG, FPM / SPM / OPM, the work images and the state of --defect-map and --sure; the
+ * steps take it and the frame's pointers. Frames stay in the
  * opponent colour space between steps (the script's processes convert to RGB files and back:
  * a 1e-5 rounding on the 0..255 scale is the only numerical difference). Unlike the script,
  * flows and masks are always recomputed (it reuses files left by a previous run).
@@ -114,7 +116,6 @@
 #include <string.h>
 #include <sys/stat.h>
 
-#include "cli_args.h"
 #include "imgio.h"
 #include "nlk_hip.h"
 #include "nlkalman.h"
@@ -282,14 +283,14 @@ static char *path_of(const char *dir, const char *pattern, int i) {
   return full;
 }
 
-static struct seq_sig sig; /* SIG, resolved on the first frame */
+static struct seq_run RUN; /* the run: options, SIG, parameters, flow settings, work images (host/seq_step.h) */
 
 /* RGB copy of an opponent-space device frame (seq_output_rgb) -> file (takes ownership of `path`); d_sum != NULL: its squared
  * error against d_clean goes to that device double first (the gt tool), d_ssim != NULL: its SSIM and those of its
  * channels to those 1 + ch device doubles (the gt tool with --ssim) */
 static void write_frame(char *path, const float *d_opp, float *d_tmp, int w, int h, int ch, double *d_sum,
                         double *d_ssim, const float *d_clean) {
-  CHK(seq_output_rgb(C, d_tmp, d_opp, w, h, ch, &sig));
+  CHK(seq_output_rgb(C, d_tmp, d_opp, w, h, ch, &RUN.sig));
   if (d_sum) CHK(nlk_dev_sqdiff_sum(C, d_sum, d_clean, d_tmp, (size_t)w * h * ch));
   if (d_ssim) CHK(nlk_dev_ssim(C, d_ssim, NULL, d_clean, d_tmp, w, h, ch, 255.f));
   write_dev(path, d_tmp, w, h, ch);
@@ -412,19 +413,17 @@ static int finish_gt(const char *out, const double *d_sums, const double *d_ssim
 
 /* ---- --sure: the error estimate of every forward step without clean frames (seq_sure_step, host/seq_step.h) */
 static struct {
-  int on;
-  struct seq_sure u;
   double *d_terms; /* [frame][pass: flt1, flt2][ch][2] device doubles, downloaded once at the end */
-  int nframes, ffr, stp, w, h, ch;
+  int nframes, ffr, stp;
 } S;
 
 /* OUT/measures-sure, every value "%.9g": per pass "F1 I MSE_hat PSNR_hat R/N div" for every frame I, then
  * "F1 total ..." = the means of MSE_hat, R/N and div over the frames and the PSNR of that mean MSE_hat (at 255); the gt
  * tool adds a last stdout line "sure T_F1 T_F2", the two mean MSE_hat. rc: what the run returns without --sure */
 static int finish_sure(const char *out, int rc) {
-  if (!S.on || rc) return rc;
+  if (!RUN.opts.sure || rc) return rc;
   static const char *label[2] = {"F1", "F2"};
-  const size_t per = (size_t)4 * S.ch;
+  const size_t per = (size_t)4 * RUN.ch;
   double *terms = malloc(sizeof(double) * per * S.nframes), tot[2];
   CHK(nlk_d2h(C, terms, S.d_terms, sizeof(double) * per * S.nframes));
   char *path = path_of(out, "measures-sure", 0);
@@ -433,8 +432,8 @@ static int finish_sure(const char *out, int rc) {
   for (int p = 0; p < 2; ++p) {
     double m = 0.0, r = 0.0, d = 0.0;
     for (int t = 0; t < S.nframes; ++t) {
-      const struct seq_sure_est e =
-          seq_sure_estimate(terms + t * per + (size_t)p * 2 * S.ch, S.w, S.h, S.ch, sig.sigma, S.u.eps_rel);
+      const struct seq_sure_est e = seq_sure_estimate(terms + t * per + (size_t)p * 2 * RUN.ch, RUN.w, RUN.h, RUN.ch,
+                                                      RUN.sig.sigma, RUN.sure.eps_rel);
       fprintf(f, "%s %d %.9g %.9g %.9g %.9g\n", label[p], S.ffr + t * S.stp, e.mse, e.psnr, e.resid, e.div);
       m += e.mse; r += e.resid; d += e.div;
     }
@@ -452,99 +451,46 @@ static int finish_sure(const char *out, int rc) {
 
 int main(int argc, const char **argv) {
   const int gt = NLK_SEQ_GT, lsmo = NLK_SEQ_LSMO;
-  int want_ssim = 0, lag1 = SEQ_LAG1_TVL1, of = SEQ_OF_TVL1;
-  if (argc > 1 && !strcmp(argv[1], "--of")) { /* in front of every other option; the run's flow estimator */
-    if (argc < 3 || (of = seq_of_mode(argv[2])) < 0) {
-      fprintf(stderr, SEQ_OF_WANT, PROG, argc < 3 ? "" : argv[2]);
+  int want_ssim = 0, lag1 = SEQ_LAG1_TVL1;
+  /* the shared options, once each in the order of seq_opts_read's table (--of, --despike, --defect-map, --sure), then
+   * the tool's own; one out of place is left for the usage text or the positional arguments */
+  int at = 1;
+  for (int from = 0, n; (n = seq_opts_read(&RUN.opts, argc, argv, at, &from, PROG)) != 0; at += n)
+    if (n < 0) return 1;
+  if (lsmo && at < argc && !strcmp(argv[at], "--flow")) { /* the positional arguments follow its value */
+    if (at + 1 >= argc || !(lag1 = seq_lag1_mode(argv[at + 1]))) {
+      fprintf(stderr, "%s: --flow %s: want tvl1 or inv\n", PROG, at + 1 >= argc ? "" : argv[at + 1]);
       return 1;
     }
-    argv[2] = argv[0];
-    argv += 2;
-    argc -= 2;
+    at += 2;
   }
-  float despike_k = 0.f;
-  int despike_r = 1;
-  if (argc > 1 && !strcmp(argv[1], "--despike")) { /* after --of, in front of --sure */
-    if (argc < 3 || seq_despike_parse(argv[2], &despike_k, &despike_r)) {
-      fprintf(stderr, SEQ_DESPIKE_WANT, PROG, argc < 3 ? "" : argv[2]);
-      return 1;
-    }
-    argv[2] = argv[0];
-    argv += 2;
-    argc -= 2;
-  }
-  float defect_k = 0.f;
-  int defect_r = 1, defect_n = SEQ_DEFECT_N;
-  if (argc > 1 && !strcmp(argv[1], "--defect-map")) { /* after --despike, in front of --sure */
-    if (argc < 3 || seq_defect_parse(argv[2], &defect_k, &defect_r, &defect_n)) {
-      fprintf(stderr, SEQ_DEFECT_WANT, PROG, argc < 3 ? "" : argv[2]);
-      return 1;
-    }
-    argv[2] = argv[0];
-    argv += 2;
-    argc -= 2;
-  }
-  if (argc > 1 && !strcmp(argv[1], "--sure")) { /* after --defect-map, in front of the rest */
-    S.on = 1;
-    argv[1] = argv[0];
-    ++argv;
-    --argc;
-  }
-  if (lsmo && argc > 1 && !strcmp(argv[1], "--flow")) { /* the positional arguments follow its value */
-    if (argc < 3 || !(lag1 = seq_lag1_mode(argv[2]))) {
-      fprintf(stderr, "%s: --flow %s: want tvl1 or inv\n", PROG, argc < 3 ? "" : argv[2]);
-      return 1;
-    }
-    argv[2] = argv[0];
-    argv += 2;
-    argc -= 2;
-  }
-  if (gt && argc > 1 && !strcmp(argv[1], "--ssim")) { /* the positional arguments follow it */
+  if (gt && at < argc && !strcmp(argv[at], "--ssim")) { /* the positional arguments follow it */
     want_ssim = 1;
-    argv[1] = argv[0];
-    ++argv;
-    --argc;
+    ++at;
   }
+  argv[at - 1] = argv[0]; /* argv[1 ..]: the positional arguments */
+  argv += at - 1;
+  argc -= at - 1;
   if (argc < 6) {
-    if (gt)
-      fprintf(stderr, "usage: %s [--of tvl1|bm] [--sure] [--ssim] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
-                      "  one-process equivalent of scripts/nlkalman-seq-gt.sh (see the header of main_seq.c)\n"
-                      "  --despike K[,R] (after --of, in front of --sure): a sample more than K sigma outside its ring's range (radius\n"
-                      "  R = 1 | 2) becomes the ring's median before the filter sees the frame: stuck, hot and dead pixels (K = 4: the\n"
-                      "  value of DESIGN.md's table)\n"
-                      "  --defect-map K[,R[,N]] (after --despike, in front of --sure): a defect map learned over time: where the mean\n"
-                      "  of the noisy frames before (window N = 2 .. 4096, default 32) lies more than K sigma / sqrt(frames) outside\n"
-                      "  its ring's range, the frame's sample becomes its ring's median (K = 4: the value of DESIGN.md's table)\n"
-                      "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
-                      "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
-    else if (lsmo)
-      fprintf(stderr, "usage: %s [--of tvl1|bm] [--sure] [--flow tvl1|inv] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]\n"
-                      "  one-process equivalent of scripts/nlkalman-lsmo-seq.sh (see the header of main_seq.c)\n"
-                      "  --despike K[,R] (after --of, in front of --sure): a sample more than K sigma outside its ring's range (radius\n"
-                      "  R = 1 | 2) becomes the ring's median before the filter sees the frame: stuck, hot and dead pixels (K = 4: the\n"
-                      "  value of DESIGN.md's table)\n"
-                      "  --defect-map K[,R[,N]] (after --despike, in front of --sure): a defect map learned over time: where the mean\n"
-                      "  of the noisy frames before (window N = 2 .. 4096, default 32) lies more than K sigma / sqrt(frames) outside\n"
-                      "  its ring's range, the frame's sample becomes its ring's median (K = 4: the value of DESIGN.md's table)\n"
-                      "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
-                      "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
-    else
-      fprintf(stderr, "usage: %s [--of tvl1|bm] [--sure] SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]\n"
-                      "  one-process equivalent of scripts/nlkalman-seq.sh (see the header of main_seq.c)\n"
-                      "  --despike K[,R] (after --of, in front of --sure): a sample more than K sigma outside its ring's range (radius\n"
-                      "  R = 1 | 2) becomes the ring's median before the filter sees the frame: stuck, hot and dead pixels (K = 4: the\n"
-                      "  value of DESIGN.md's table)\n"
-                      "  --defect-map K[,R[,N]] (after --despike, in front of --sure): a defect map learned over time: where the mean\n"
-                      "  of the noisy frames before (window N = 2 .. 4096, default 32) lies more than K sigma / sqrt(frames) outside\n"
-                      "  its ring's range, the frame's sample becomes its ring's median (K = 4: the value of DESIGN.md's table)\n"
-                      "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
-                      "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0]);
+    fprintf(stderr, "usage: %s [--of tvl1|bm] [--sure] %s\n"
+                    "  one-process equivalent of scripts/%s.sh (see the header of main_seq.c)\n"
+                    "  --despike K[,R] (after --of, in front of --sure): a sample more than K sigma outside its ring's range (radius\n"
+                    "  R = 1 | 2) becomes the ring's median before the filter sees the frame: stuck, hot and dead pixels (K = 4: the\n"
+                    "  value of DESIGN.md's table)\n"
+                    "  --defect-map K[,R[,N]] (after --despike, in front of --sure): a defect map learned over time: where the mean\n"
+                    "  of the noisy frames before (window N = 2 .. 4096, default 32) lies more than K sigma / sqrt(frames) outside\n"
+                    "  its ring's range, the frame's sample becomes its ring's median (K = 4: the value of DESIGN.md's table)\n"
+                    "  --sure: OUT/measures-sure gets the Monte-Carlo SURE estimate of every flt1 / flt2 frame's error, made without\n"
+                    "  clean frames (under SIG = vst | nlf: in the stabilised domain, at the run's sigma)\n", argv[0],
+            gt ? "[--ssim] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]"
+            : lsmo ? "[--flow tvl1|inv] SEQ FFR LFR SIG OUT [FPM [SPM [OPM]]]" : "SEQ FFR LFR SIG OUT [STP [FPM [SPM [OPM]]]]",
+            PROG);
     return 1;
   }
   const char *seq = argv[1], *out = argv[5];
   const int ffr = atoi(argv[2]), lfr = atoi(argv[3]);
-  const int sig_bad = seq_sig_parse(argv[4], &sig);
-  const int vst = seq_sig_vst(&sig) != NULL, auto_sigma = sig.mode != SEQ_SIG_NUMBER;
+  const int sig_bad = seq_sig_parse(argv[4], &RUN.sig);
+  const int vst = seq_sig_vst(&RUN.sig) != NULL, auto_sigma = RUN.sig.mode != SEQ_SIG_NUMBER;
   if (vst && gt) {
     fprintf(stderr, "%s: SIG = vst is not supported by the ground-truth loop\n", PROG);
     return 1;
@@ -559,21 +505,15 @@ int main(int argc, const char **argv) {
   const char *fpm = argc > a0 ? argv[a0] : "", *spm = argc > a0 + 1 ? argv[a0 + 1] : "";
   const char *opm = argc > a0 + 2 && argv[a0 + 2][0] ? argv[a0 + 2]
                     : gt ? "1 0.40 0.75 1 0.40 0.75" : "1 0.25 0.75 1 0.25 0.75";
-  int fs1 = 1, fs2 = 1;
-  float dw1 = 0.25f, th1 = 0.75f, dw2 = 0.25f, th2 = 0.75f;
-  if (sscanf(opm, "%d %f %f %d %f %f", &fs1, &dw1, &th1, &fs2, &dw2, &th2) != 6) {
+  if (seq_parse_opm(opm, &RUN.bwd, &RUN.fwd, 0)) {
     fprintf(stderr, "%s: OPM must hold 6 numbers: FSCALE1 DW1 TH1 FSCALE2 DW2 TH2\n", PROG);
     return 1;
   }
   const int smoothing = strcmp(spm, "no") != 0;
 
   /* filter / smoother parameters: the options of nlkalman-flt and nlkalman-smo, same grammar */
-  struct nlkalman_params f1, f2, s1;
-  cli_params_unset(&f1); cli_params_unset(&f2); cli_params_unset(&s1);
   int verbose = 0;
-  seq_parse_fpm("nlkalman-seq (FPM)", fpm, &f1, &f2, &verbose);
-  if (smoothing) seq_parse_spm("nlkalman-seq (SPM)", spm, &s1, &verbose);
-  if (f1.patch_sz == 0 || f2.patch_sz == 0) {
+  if (seq_run_params(&RUN, "nlkalman-seq (FPM)", fpm, "nlkalman-seq (SPM)", smoothing ? spm : NULL, &verbose)) {
     fprintf(stderr, "nlkalman-seq: both filtering iterations are needed (f1_p, f2_p != 0)\n");
     return 1;
   }
@@ -594,10 +534,9 @@ int main(int argc, const char **argv) {
   wq_start();
   int w = 0, h = 0, ch = 0;
   size_t bytes = 0;
-  struct seq_work W = {0};
-  struct seq_defects D = {0};
+  const struct seq_work *const W = &RUN.work;
   float *d_rgb = NULL, *flt1 = NULL;
-  float *d_lsm1 = NULL; /* lsmo: the smoothed frame (its flow and mask are W.d_fflow, W.d_focc) */
+  float *d_lsm1 = NULL; /* lsmo: the smoothed frame (its flow and mask are W->d_fflow, W->d_focc) */
   float **flt2 = calloc(nframes, sizeof(float *));  /* kept for the backward pass */
   /* gt: the clean frames (all of them kept for the smoother's measures, else one buffer), the squared-error
    * sums [pass][frame] (flt1, flt2, smo1) and the output names */
@@ -637,15 +576,13 @@ int main(int argc, const char **argv) {
         d_ssims = (double *)d;
       }
       d_rgb = dev_frame(bytes);
-      CHK(seq_work_alloc(C, &W, w, h, ch, lsmo && smoothing));
-      if (defect_k != 0.f) CHK(seq_defects_alloc(C, &D, defect_k, defect_r, defect_n, w, h, ch));
+      CHK(seq_run_open(&RUN, C, w, h, ch, lsmo && smoothing));
       if (lsmo && smoothing) d_lsm1 = dev_frame(bytes);
-      if (S.on) {
+      if (RUN.opts.sure) {
         void *d = NULL;
-        CHK(seq_sure_alloc(C, &S.u, w, h, ch, 0));
         CHK(nlk_dev_alloc(C, &d, sizeof(double) * 4 * ch * nframes));
         S.d_terms = (double *)d;
-        S.nframes = nframes; S.ffr = ffr; S.stp = stp; S.w = w; S.h = h; S.ch = ch;
+        S.nframes = nframes; S.ffr = ffr; S.stp = stp;
       }
       pool_init(bytes > (size_t)w * h * 8 ? bytes : (size_t)w * h * 8);
       if (Q.nthreads > 0) {
@@ -682,7 +619,7 @@ int main(int argc, const char **argv) {
         fprintf(stderr, "%s: SIG = %s needs the noisy frame %s (there is no sigma to make it with)\n", PROG, argv[4], npath);
         return 1;
       } else {
-        CHK(nlk_dev_awgn(C, d_rgb, clean[t], (size_t)w * h * ch, sig.sigma, seed0 + (uint32_t)i));
+        CHK(nlk_dev_awgn(C, d_rgb, clean[t], (size_t)w * h * ch, RUN.sig.sigma, seed0 + (uint32_t)i));
         write_dev(npath, d_rgb, w, h, ch);
       }
     }
@@ -693,34 +630,28 @@ int main(int argc, const char **argv) {
       ra_start(next);
     }
     if (t == 0) { /* sigma is known once the first frame is on the device, then every default that depends on it */
-      const int rc = seq_sig_resolve(C, &sig, d_rgb, w, h, ch, stdout, PROG);
+      const int rc = seq_run_first_frame(&RUN, d_rgb, stdout, PROG);
       if (rc == SEQ_SIG_REFUSED) return 1;
       CHK(rc);
-      seq_default_params(&f1, &f2, &s1, sig.sigma);
     }
     float *n1 = dev_frame(bytes), *n2 = dev_frame(bytes);
-    const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .of = of, .sig = &sig, .f1 = &f1, .f2 = &f2,
-                                  .fscale = fs1, .dw = dw1, .th = th1, .work = &W,
-                                  .defects = defect_k != 0.f ? &D : NULL,
-                                  .despike_k = despike_k, .despike_r = despike_r, .d_rgb = d_rgb,
-                                  .prev_flt1 = t ? flt1 : NULL, .prev_flt2 = t ? flt2[t - 1] : NULL,
+    const struct seq_step step = {.d_rgb = d_rgb, .prev_flt1 = t ? flt1 : NULL, .prev_flt2 = t ? flt2[t - 1] : NULL,
                                   .flt1 = n1, .flt2 = n2};
-    CHK(seq_forward_step(&step));
-    if (S.on) CHK(seq_sure_step(&step, &S.u, t, S.d_terms + (size_t)t * 4 * ch));
+    CHK(seq_forward_step(&RUN, &step));
+    if (RUN.opts.sure) CHK(seq_sure_step(&RUN, &step, t, S.d_terms + (size_t)t * 4 * ch));
     if (t > 0) { /* the flow and its mask (script lines 57-73) */
-      write_dev(path_of(out, lsmo ? "bflo-%03d.flo" : "bflo1-%03d.flo", i), W.d_flow, w, h, 2);
-      write_dev(path_of(out, lsmo ? "bocc-%03d.png" : "bocc1-%03d.png", i), W.d_occ, w, h, 1);
+      write_dev(path_of(out, lsmo ? "bflo-%03d.flo" : "bflo1-%03d.flo", i), W->d_flow, w, h, 2);
+      write_dev(path_of(out, lsmo ? "bocc-%03d.png" : "bocc1-%03d.png", i), W->d_occ, w, h, 1);
     }
-    write_frame(path_of(out, OUTNAME("flt1"), i), n1, W.d_tmp, w, h, ch, SUM(0, t), SSIM(0, t), clean[t]);
-    write_frame(path_of(out, OUTNAME("flt2"), i), n2, W.d_tmp, w, h, ch, SUM(1, t), SSIM(1, t), clean[t]);
+    write_frame(path_of(out, OUTNAME("flt1"), i), n1, W->d_tmp, w, h, ch, SUM(0, t), SSIM(0, t), clean[t]);
+    write_frame(path_of(out, OUTNAME("flt2"), i), n2, W->d_tmp, w, h, ch, SUM(1, t), SSIM(1, t), clean[t]);
     if (lsmo && smoothing && t > 0) { /* smooth the previous frame (script lines 87-108) */
-      const struct seq_lag1 lag = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = lag1, .of = of,
-                                   .fscale = fs2, .dw = dw2, .th = th2, .work = &W, .d_fflow = W.d_fflow,
-                                   .d_focc = W.d_focc, .flt2 = flt2[t - 1], .next = n2, .smo1 = d_lsm1};
-      CHK(seq_lag1_step(&lag));
-      write_dev(path_of(out, "fflo-%03d.flo", i), W.d_fflow, w, h, 2);
-      write_dev(path_of(out, "focc-%03d.png", i), W.d_focc, w, h, 1);
-      write_frame(path_of(out, "lsm1-%03d.tif", i - 1), d_lsm1, W.d_tmp, w, h, ch, NULL, NULL, NULL);
+      const struct seq_lag1 lag = {.mode = lag1, .d_fflow = W->d_fflow, .d_focc = W->d_focc, .flt2 = flt2[t - 1],
+                                   .next = n2, .smo1 = d_lsm1};
+      CHK(seq_lag1_step(&RUN, &lag));
+      write_dev(path_of(out, "fflo-%03d.flo", i), W->d_fflow, w, h, 2);
+      write_dev(path_of(out, "focc-%03d.png", i), W->d_focc, w, h, 1);
+      write_frame(path_of(out, "lsm1-%03d.tif", i - 1), d_lsm1, W->d_tmp, w, h, ch, NULL, NULL, NULL);
       if (verbose) printf("frame %d smoothed\n", i - 1);
     }
     if (flt1) nlk_dev_free(C, flt1);
@@ -730,7 +661,7 @@ int main(int argc, const char **argv) {
     if (verbose) printf("frame %d filtered\n", i);
   }
   if (lsmo) { /* the last frame's lsm1 is its flt2 (script lines 112-116) */
-    if (smoothing) write_frame(path_of(out, "lsm1-%03d.tif", lfr), flt2[nframes - 1], W.d_tmp, w, h, ch, NULL, NULL, NULL);
+    if (smoothing) write_frame(path_of(out, "lsm1-%03d.tif", lfr), flt2[nframes - 1], W->d_tmp, w, h, ch, NULL, NULL, NULL);
     return finish_sure(out, wq_finish());
   }
   if (!smoothing) /* script line 113 */
@@ -739,18 +670,17 @@ int main(int argc, const char **argv) {
   /* ---- backward pass (script lines 117-150) */
   float **smo = calloc(nframes, sizeof(float *));
   smo[nframes - 1] = flt2[nframes - 1];
-  write_frame(path_of(out, OUTNAME("smo1"), ffr + (nframes - 1) * stp), smo[nframes - 1], W.d_tmp, w, h, ch,
+  write_frame(path_of(out, OUTNAME("smo1"), ffr + (nframes - 1) * stp), smo[nframes - 1], W->d_tmp, w, h, ch,
               SUM(2, nframes - 1), SSIM(2, nframes - 1), clean[nframes - 1]);
   for (t = nframes - 2; t >= 0; --t) {
     const int i = ffr + t * stp;
     smo[t] = dev_frame(bytes);
-    const struct seq_lag1 back = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = SEQ_LAG1_TVL1, .of = of,
-                                  .fscale = fs2, .dw = dw2, .th = th2, .work = &W, .d_fflow = W.d_flow,
-                                  .d_focc = W.d_occ, .flt2 = flt2[t], .next = smo[t + 1], .smo1 = smo[t]};
-    CHK(seq_lag1_step(&back));
-    write_dev(path_of(out, "fflo-%03d.flo", i), W.d_flow, w, h, 2);
-    write_dev(path_of(out, "focc-%03d.png", i), W.d_occ, w, h, 1);
-    write_frame(path_of(out, OUTNAME("smo1"), i), smo[t], W.d_tmp, w, h, ch, SUM(2, t), SSIM(2, t), clean[t]);
+    const struct seq_lag1 back = {.mode = SEQ_LAG1_TVL1, .d_fflow = W->d_flow, .d_focc = W->d_occ, .flt2 = flt2[t],
+                                  .next = smo[t + 1], .smo1 = smo[t]};
+    CHK(seq_lag1_step(&RUN, &back));
+    write_dev(path_of(out, "fflo-%03d.flo", i), W->d_flow, w, h, 2);
+    write_dev(path_of(out, "focc-%03d.png", i), W->d_occ, w, h, 1);
+    write_frame(path_of(out, OUTNAME("smo1"), i), smo[t], W->d_tmp, w, h, ch, SUM(2, t), SSIM(2, t), clean[t]);
     if (verbose) printf("frame %d smoothed\n", i);
   }
   return finish_sure(out, gt ? finish_gt(out, d_sums, d_ssims, 3, nframes, ch, (size_t)w * h * ch) : wq_finish());

@@ -15,6 +15,8 @@
  *                    written when frame t has been filtered; the last frame goes out as its flt2. tvl1: a second TV-L1
  *                    flow per frame, as the script; inv: the backward flow of frame t inverted (nlk_dev_flow_invert)
  *     --spm "..."    nlkalman-smo options (--s1_p ...), as nlkalman-seq's SPM
+ *     (the next four are nlkalman-seq's, read by the same seq_opts_read into the run's seq_opts, host/seq_step.h; here
+ *     in any place; a value it refuses ends the run where it stands on the command line)
  *     --of tvl1|bm   the flow estimator of the run, as nlkalman-seq's: tvl1 (default), or bm: block matching
  *                    (nlk_dev_bm_flow) for the backward flow and for --smooth tvl1's own flow; --opm's FSCALE and TH
  *                    apply, DW is ignored
@@ -61,7 +63,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "cli_args.h"
 #include "nlk_hip.h"
 #include "nlkalman.h"
 #include "seq_step.h"
@@ -208,24 +209,25 @@ static int usage(void) {
 
 int main(int argc, const char **argv) {
   const char *matrix_s = "auto", *range_s = "auto", *fpm = "", *opm = "1 0.25 0.75", *pos[3] = {NULL, NULL, NULL};
-  const char *smooth_s = NULL, *spm = "", *of_s = "tvl1", *despike_s = NULL, *defect_s = NULL;
+  const char *smooth_s = NULL, *spm = "";
   long max_frames = -1;
-  int copy = 0, want_probe = 0, verbose = 0, npos = 0, want_sure = 0;
+  int copy = 0, want_probe = 0, verbose = 0, npos = 0;
+  static struct seq_run R; /* the run: options, SIG, parameters, flow settings, work images (host/seq_step.h) */
   for (int i = 1; i < argc; ++i) {
     const char *a = argv[i];
     const char **val = NULL;
+    const int shared = seq_opts_arity(a); /* --of, --despike, --defect-map, --sure: nlkalman-seq's, here in any place */
     if (!strcmp(a, "--matrix")) val = &matrix_s;
     else if (!strcmp(a, "--range")) val = &range_s;
     else if (!strcmp(a, "--fpm")) val = &fpm;
     else if (!strcmp(a, "--opm")) val = &opm;
     else if (!strcmp(a, "--smooth")) val = &smooth_s;
     else if (!strcmp(a, "--spm")) val = &spm;
-    else if (!strcmp(a, "--of")) val = &of_s;
-    else if (!strcmp(a, "--despike")) val = &despike_s;
-    else if (!strcmp(a, "--defect-map")) val = &defect_s;
-    if (val) {
-      if (++i >= argc) { fprintf(stderr, "%s: %s needs a value\n", PROG, a); return 1; }
-      *val = argv[i];
+    if (val || shared) {
+      if ((val || shared == 2) && i + 1 >= argc) { fprintf(stderr, "%s: %s needs a value\n", PROG, a); return 1; }
+      if (val) *val = argv[++i];
+      else if (seq_opts_read(&R.opts, argc, argv, i, NULL, PROG) < 0) return 1;
+      else i += shared - 1;
     } else if (!strcmp(a, "--frames")) {
       char *e;
       if (++i >= argc || (max_frames = strtol(argv[i], &e, 10)) < 0 || *e || e == argv[i]) {
@@ -234,7 +236,6 @@ int main(int argc, const char **argv) {
       }
     } else if (!strcmp(a, "--copy")) copy = 1;
     else if (!strcmp(a, "--probe")) want_probe = 1;
-    else if (!strcmp(a, "--sure")) want_sure = 1;
     else if (!strcmp(a, "-v")) verbose = 1;
     else if (!strcmp(a, "-h") || !strcmp(a, "--help")) { usage(); return 0; }
     else if (a[0] == '-' && a[1] && !(npos == 0 && (a[1] == '.' || (a[1] >= '0' && a[1] <= '9')))) {
@@ -244,39 +245,17 @@ int main(int argc, const char **argv) {
     else return usage();
   }
   if (npos < 1) return usage();
-  struct seq_sig sig;
-  if (seq_sig_parse(pos[0], &sig)) {
+  if (seq_sig_parse(pos[0], &R.sig)) {
     fprintf(stderr, SEQ_SIG_WANT, PROG, pos[0]);
     return 1;
   }
-  int fs = 1, fs2 = 1;
-  float dw = 0.25f, th = 0.75f, dw2 = 0.25f, th2 = 0.75f;
-  const int nopm = sscanf(opm, "%d %f %f %d %f %f", &fs, &dw, &th, &fs2, &dw2, &th2);
-  if (nopm != 3 && nopm != 6) {
+  if (seq_parse_opm(opm, &R.bwd, &R.fwd, 1)) {
     fprintf(stderr, "%s: --opm must hold 3 or 6 numbers: FSCALE DW TH [FSCALE2 DW2 TH2]\n", PROG);
     return 1;
   }
-  if (nopm == 3) { fs2 = fs; dw2 = dw; th2 = th; }
   int smooth = SEQ_LAG1_OFF;
   if (smooth_s && !(smooth = seq_lag1_mode(smooth_s))) {
     fprintf(stderr, "%s: --smooth %s: want tvl1 or inv\n", PROG, smooth_s);
-    return 1;
-  }
-  const int of = seq_of_mode(of_s);
-  if (of < 0) {
-    fprintf(stderr, SEQ_OF_WANT, PROG, of_s);
-    return 1;
-  }
-  float despike_k = 0.f;
-  int despike_r = 1;
-  if (despike_s && seq_despike_parse(despike_s, &despike_k, &despike_r)) {
-    fprintf(stderr, SEQ_DESPIKE_WANT, PROG, despike_s);
-    return 1;
-  }
-  float defect_k = 0.f;
-  int defect_r = 1, defect_n = SEQ_DEFECT_N;
-  if (defect_s && seq_defect_parse(defect_s, &defect_k, &defect_r, &defect_n)) {
-    fprintf(stderr, SEQ_DEFECT_WANT, PROG, defect_s);
     return 1;
   }
   int matrix = 0, range = -1;
@@ -286,13 +265,7 @@ int main(int argc, const char **argv) {
   if (!strcmp(range_s, "limited")) range = 0;
   else if (!strcmp(range_s, "full")) range = 1;
   else if (strcmp(range_s, "auto")) { fprintf(stderr, "%s: --range %s: want limited, full or auto\n", PROG, range_s); return 1; }
-  struct nlkalman_params f1, f2;
-  cli_params_unset(&f1); cli_params_unset(&f2);
-  seq_parse_fpm(PROG " (--fpm)", fpm, &f1, &f2, &verbose);
-  struct nlkalman_params s1;
-  cli_params_unset(&s1);
-  if (smooth) seq_parse_spm(PROG " (--spm)", spm, &s1, &verbose);
-  if (f1.patch_sz == 0 || f2.patch_sz == 0) {
+  if (seq_run_params(&R, PROG " (--fpm)", fpm, PROG " (--spm)", smooth ? spm : NULL, &verbose)) {
     fprintf(stderr, "%s: both filtering iterations are needed (f1_p, f2_p != 0)\n", PROG);
     return 1;
   }
@@ -344,25 +317,22 @@ int main(int argc, const char **argv) {
     return 1;
   }
 
-  if (copy) smooth = SEQ_LAG1_OFF; /* (nothing is filtered) */
-  struct seq_work W;
-  CHK(seq_work_alloc(C, &W, w, h, ch, smooth));
-  struct seq_defects D = {0};
-  if (defect_k != 0.f && !copy) CHK(seq_defects_alloc(C, &D, defect_k, defect_r, defect_n, w, h, ch));
+  if (copy) { /* (nothing is filtered) */
+    smooth = SEQ_LAG1_OFF;
+    R.opts.defect_k = 0.f;
+    R.opts.sure = 0;
+  }
+  CHK(seq_run_open(&R, C, w, h, ch, smooth));
+  const struct seq_work *const W = &R.work;
   /* the codes; the RGB frame, flt1 and flt2 of this frame and the previous one, by turns, --smooth: the smoothed frame */
   void *d_yuv = NULL, *fr[6] = {0};
   CHK(nlk_dev_alloc(C, &d_yuv, hd.frame_bytes));
   for (int i = 0; i < (smooth ? 6 : 5); ++i) CHK(nlk_dev_alloc(C, &fr[i], bytes));
   float *d_rgb = fr[0], *flt1[2] = {fr[1], fr[2]}, *flt2[2] = {fr[3], fr[4]}, *d_lsm1 = fr[5];
-  /* --sure: the probe's images, the terms of one frame (flt1's, then flt2's) and the sums of the lines printed */
-  struct seq_sure U = {0};
+  /* --sure: the terms of one frame (flt1's, then flt2's) and the sums of the lines printed */
   void *d_terms = NULL;
   double sure_sum[3] = {0.0, 0.0, 0.0};
-  if (copy) want_sure = 0; /* (nothing is filtered) */
-  if (want_sure) {
-    CHK(seq_sure_alloc(C, &U, w, h, ch, 0));
-    CHK(nlk_dev_alloc(C, &d_terms, sizeof(double) * 4 * ch));
-  }
+  if (R.opts.sure) CHK(nlk_dev_alloc(C, &d_terms, sizeof(double) * 4 * ch));
 
   long t = 0;
   int failed = 0;
@@ -373,34 +343,28 @@ int main(int argc, const char **argv) {
     CHK(nlk_dev_yuv_to_rgb(C, d_rgb, d_yuv, w, h, &hd.fmt));
     if (!copy) {
       if (t == 0) { /* sigma is known once the first frame is on the device, then every default that depends on it */
-        const int rc = seq_sig_resolve(C, &sig, d_rgb, w, h, ch, stderr, PROG);
+        const int rc = seq_run_first_frame(&R, d_rgb, stderr, PROG);
         if (rc == SEQ_SIG_REFUSED) { failed = 1; break; }
         CHK(rc);
-        seq_default_params(&f1, &f2, &s1, sig.sigma);
       }
       const int cur = (int)(t & 1), prv = cur ^ 1;
-      const struct seq_step step = {.ctx = C, .w = w, .h = h, .ch = ch, .of = of, .sig = &sig, .f1 = &f1, .f2 = &f2,
-                                    .fscale = fs, .dw = dw, .th = th, .work = &W,
-                                    .defects = defect_k != 0.f ? &D : NULL,
-                                    .despike_k = despike_k, .despike_r = despike_r, .d_rgb = d_rgb,
-                                    .prev_flt1 = t ? flt1[prv] : NULL, .prev_flt2 = t ? flt2[prv] : NULL,
+      const struct seq_step step = {.d_rgb = d_rgb, .prev_flt1 = t ? flt1[prv] : NULL, .prev_flt2 = t ? flt2[prv] : NULL,
                                     .flt1 = flt1[cur], .flt2 = flt2[cur]};
-      CHK(seq_forward_step(&step));
-      if (want_sure) {
+      CHK(seq_forward_step(&R, &step));
+      if (R.opts.sure) {
         double terms[4 * SEQ_SIG_MAX_CH];
-        CHK(seq_sure_step(&step, &U, t, (double *)d_terms));
+        CHK(seq_sure_step(&R, &step, t, (double *)d_terms));
         CHK(nlk_d2h(C, terms, d_terms, sizeof(double) * 4 * ch));
-        const struct seq_sure_est e = seq_sure_estimate(terms + 2 * ch, w, h, ch, sig.sigma, U.eps_rel);
+        const struct seq_sure_est e = seq_sure_estimate(terms + 2 * ch, w, h, ch, R.sig.sigma, R.sure.eps_rel);
         fprintf(stderr, "sure %ld %.9g %.9g %.9g %.9g\n", t + 1, e.mse, e.psnr, e.resid, e.div);
         sure_sum[0] += e.mse; sure_sum[1] += e.resid; sure_sum[2] += e.div;
       }
       if (smooth) { /* frame t - 1 goes out smoothed, into its own buffer; frame t waits for the next one */
         if (t > 0) {
-          const struct seq_lag1 lag = {.ctx = C, .w = w, .h = h, .ch = ch, .sig = &sig, .s1 = &s1, .mode = smooth, .of = of,
-                                       .fscale = fs2, .dw = dw2, .th = th2, .work = &W, .d_fflow = W.d_fflow,
-                                       .d_focc = W.d_focc, .flt2 = flt2[prv], .next = flt2[cur], .smo1 = d_lsm1};
-          CHK(seq_lag1_step(&lag));
-          if (emit(frame_buf(t - 1), d_lsm1, W.d_tmp, d_yuv, &hd, ch, &sig)) return 1;
+          const struct seq_lag1 lag = {.mode = smooth, .d_fflow = W->d_fflow, .d_focc = W->d_focc, .flt2 = flt2[prv],
+                                       .next = flt2[cur], .smo1 = d_lsm1};
+          CHK(seq_lag1_step(&R, &lag));
+          if (emit(frame_buf(t - 1), d_lsm1, W->d_tmp, d_yuv, &hd, ch, &R.sig)) return 1;
           frame_put(t - 1);
           if (verbose) fprintf(stderr, "frame %ld smoothed\n", t);
         }
@@ -413,7 +377,7 @@ int main(int argc, const char **argv) {
       }
     }
     /* --copy: the RGB frame goes back as it is */
-    if (emit(buf, copy ? d_rgb : flt2[t & 1], W.d_tmp, d_yuv, &hd, ch, copy ? NULL : &sig)) return 1;
+    if (emit(buf, copy ? d_rgb : flt2[t & 1], W->d_tmp, d_yuv, &hd, ch, copy ? NULL : &R.sig)) return 1;
     frame_put(t);
     if (verbose) fprintf(stderr, "frame %ld %s\n", t + 1, copy ? "converted" : "filtered");
     if (write_has_failed()) { /* nobody reads the output any more: stop filtering (the process ends, threads and all) */
@@ -422,7 +386,7 @@ int main(int argc, const char **argv) {
     }
   }
   if (smooth && t > 0 && !failed) { /* the last frame goes out as its flt2 */
-    if (emit(frame_buf(t - 1), flt2[(t - 1) & 1], W.d_tmp, d_yuv, &hd, ch, &sig)) return 1;
+    if (emit(frame_buf(t - 1), flt2[(t - 1) & 1], W->d_tmp, d_yuv, &hd, ch, &R.sig)) return 1;
     frame_put(t - 1);
   }
   if (G.threads) {
@@ -430,7 +394,7 @@ int main(int argc, const char **argv) {
     pthread_join(th_w, NULL);
     /* after an early `break` the reader may still wait for a slot: the process ends without joining it */
   }
-  if (want_sure && t > 0 && !failed)
+  if (R.opts.sure && t > 0 && !failed)
     fprintf(stderr, "sure total %.9g %.9g %.9g %.9g\n", sure_sum[0] / t, 10.0 * log10(255.0 * 255.0 * t / sure_sum[0]),
             sure_sum[1] / t, sure_sum[2] / t);
   if (fflush(out) || (out != stdout && fclose(out))) { fprintf(stderr, "%s: write error\n", PROG); failed = 1; }
@@ -439,11 +403,7 @@ int main(int argc, const char **argv) {
   nlk_dev_free(C, d_yuv);
   for (int i = 0; i < 6; ++i)
     if (fr[i]) nlk_dev_free(C, fr[i]);
-  if (want_sure) {
-    seq_sure_free(C, &U);
-    nlk_dev_free(C, d_terms);
-  }
-  seq_defects_free(C, &D);
-  seq_work_free(C, &W);
+  if (d_terms) nlk_dev_free(C, d_terms);
+  seq_run_close(&R);
   return failed;
 }

@@ -1,5 +1,6 @@
-/* seq_args.c — the grammar of the sequence tools' SIG argument and of --despike's and --defect-map's values (seq_step.h). Plain C: nothing of the device libraries
- * is needed to link it. */
+/* seq_args.c — the grammar of the sequence tools' SIG argument, of --of's, --despike's and --defect-map's values and the
+ * one reader of the options all four tools share (seq_step.h). Plain C: nothing of the device libraries is needed to
+ * link it. */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -57,5 +58,57 @@ int seq_defect_parse(const char *text, float *k, int *r, int *n) {
   *k = v;
   *r = radius;
   *n = window;
+  return 0;
+}
+
+int seq_of_mode(const char *name) {
+  if (name && !strcmp(name, "tvl1")) return SEQ_OF_TVL1;
+  if (name && !strcmp(name, "bm")) return SEQ_OF_BM;
+  return -1;
+}
+
+/* ---- the shared options: one row each, in the order main_seq.c admits them */
+static int opt_of(const char *text, struct seq_opts *o) {
+  const int of = seq_of_mode(text);
+  if (of >= 0) o->of = of;
+  return of < 0;
+}
+static int opt_despike(const char *text, struct seq_opts *o) { return seq_despike_parse(text, &o->despike_k, &o->despike_r); }
+static int opt_defect(const char *text, struct seq_opts *o) {
+  return seq_defect_parse(text, &o->defect_k, &o->defect_r, &o->defect_n);
+}
+static int opt_sure(const char *text, struct seq_opts *o) {
+  (void)text;
+  o->sure = 1;
+  return 0;
+}
+static const struct {
+  const char *name;
+  int arity;        /* entries of argv: 1 a flag, 2 an option and its value */
+  const char *want; /* the line of a refused or missing value (prog, text) */
+  int (*set)(const char *text, struct seq_opts *o);
+} seq_opt_rows[] = {{"--of", 2, SEQ_OF_WANT, opt_of},
+                    {"--despike", 2, SEQ_DESPIKE_WANT, opt_despike},
+                    {"--defect-map", 2, SEQ_DEFECT_WANT, opt_defect},
+                    {"--sure", 1, NULL, opt_sure}};
+#define SEQ_OPT_ROWS ((int)(sizeof seq_opt_rows / sizeof seq_opt_rows[0]))
+
+int seq_opts_arity(const char *name) {
+  for (int i = 0; i < SEQ_OPT_ROWS; ++i)
+    if (!strcmp(name, seq_opt_rows[i].name)) return seq_opt_rows[i].arity;
+  return 0;
+}
+
+int seq_opts_read(struct seq_opts *o, int argc, const char **argv, int at, int *from, const char *prog) {
+  for (int i = from ? *from : 0; at < argc && i < SEQ_OPT_ROWS; ++i) {
+    if (strcmp(argv[at], seq_opt_rows[i].name)) continue;
+    const char *text = seq_opt_rows[i].arity == 2 && at + 1 < argc ? argv[at + 1] : NULL;
+    if (seq_opt_rows[i].set(text, o)) {
+      fprintf(stderr, seq_opt_rows[i].want, prog, text ? text : "");
+      return -1;
+    }
+    if (from) *from = i + 1;
+    return seq_opt_rows[i].arity;
+  }
   return 0;
 }
