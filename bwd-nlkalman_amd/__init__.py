@@ -562,7 +562,7 @@ class Context:
         self._chk(self.L.nlk_ctx_set_deterministic(self.h, int(on)))
 
     def last_group_shape(self):
-        """What the last group launch ran (nlk_ctx_last_group_shape): family "k_group8m" / "k_group8" / None (another
+        """What the last group launch ran (nlk_ctx_last_group_shape): family "k_group8m" / None (another
         launcher), sep, tgx, tgy, ntx, nty, nty_full, single, passes, chase (reach of the replay inside the launch, 0 =
         not in it), far = (tgx, tgy) of deterministic mode's far pass or None, packed_lists / packed_far = the launch / its far
         pass read the lists packed (nlk_ctx_last_group_packed)."""
@@ -570,7 +570,7 @@ class Context:
         self._chk(self.L.nlk_ctx_last_group_shape(self.h, out))
         v = list(out)
         d = dict(zip(("sep", "tgx", "tgy", "ntx", "nty", "nty_full", "single", "passes", "chase"), v[1:10]))
-        d["family"] = {1: "k_group8m", 2: "k_group8"}.get(v[0])
+        d["family"] = {1: "k_group8m"}.get(v[0])
         d["far"] = (v[10], v[11]) if v[8] > 1 else None
         pk = self.L.nlk_ctx_last_group_packed(self.h)
         d["packed_lists"], d["packed_far"] = pk > 0 and bool(pk & 1), pk > 0 and bool(pk & 2)

@@ -46,7 +46,7 @@
 // of the 4 members of a step; one LDS read-modify-write per (member, pixel)
 // touches 16 distinct pixels in (CH + 1) distinct planes (the weight plane is
 // produced by the same path: gain 0 and the DCT of a constant-1 patch as mean),
-// so the private accumulator tile needs no atomics (k_group8.h explains the
+// so the private accumulator tile needs no atomics (k_group_tile.h explains the
 // tile and its flush).
 #pragma once
 #include "nlk_common.h"
@@ -401,7 +401,7 @@ k_group8m(const float* __restrict__ img,   // matching / statistics image (plana
     }
   }
   bool any_target = false;  // (deterministic mode: a tile without work writes no slab)
-  for (int i = lane; i < (CH + 1) * plane / 4; i += 64)  // (plane is a multiple of 16)
+  for (int i = lane; i < (CH + 1) * plane / 4; i += 64)  // ((CH + 1) * plane is a multiple of 4: tu_group8.hip, shape_pass)
     reinterpret_cast<nlk_f4*>(smem)[i] = nlk_f4{0.f, 0.f, 0.f, 0.f};
   // [CH+2][NLK_G8_SST]: gains / means between the passes ([2][4][16] floats per channel + padding). Pass B treats the weight plane as one more
   // channel (gain 0, mean = DCT of a constant-1 patch: 8 at the DC coefficient) and the unused slots

@@ -1,5 +1,15 @@
-// k_group_tile.h — what the tiled group kernels share: the launch's tile description (a kernel argument of k_group8,
+// k_group_tile.h — what the tiled group kernels share: the launch's tile description (a kernel argument of
 // k_group8m, k_groupp and the gather kernel) and the small lane helpers all of them use
+//
+// Aggregation. A workgroup is ONE wavefront that owns a tile of tgx x tgy targets
+// and a private LDS accumulator tile (ch value planes + 1 weight plane, covering
+// the tile plus the search halo). Being private, the tile is updated with plain
+// ds_read / add / ds_write (LDS float atomics retire about one lane per clock on
+// gfx950 and made an earlier, shared-tile version of the 8x8 kernel LDS-bound: see
+// profiles/). The tile is flushed once with coalesced global float atomics,
+// skipping untouched entries, which cuts the HBM atomic traffic ~10x compared
+// with one global atomic per patch pixel (global float atomics run at a fixed
+// ~1.3 TB/s of added bytes on MI355X and would otherwise bound the kernel).
 #pragma once
 #include "nlk_common.h"
 

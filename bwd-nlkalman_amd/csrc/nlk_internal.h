@@ -51,7 +51,7 @@ struct NlkRecView {
 #define NLK_UNSET (-2147483647 - 1)
 #define NLK_SWITCH_LIST(X)                                                                                   \
   X(deterministic, "NLK_DETERMINISTIC") X(generic_group, "NLK_GENERIC_GROUP") X(group_packed, "NLK_GROUP_PACKED") \
-  X(group_dpp, "NLK_GROUP_DPP") X(group_sep, "NLK_GROUP_SEP") X(group_ilp, "NLK_GROUP_ILP") X(generic_match, "NLK_GENERIC_MATCH") X(mtx, "NLK_MTX") X(mty, "NLK_MTY")    \
+  X(group_sep, "NLK_GROUP_SEP") X(group_ilp, "NLK_GROUP_ILP") X(generic_match, "NLK_GENERIC_MATCH") X(mtx, "NLK_MTX") X(mty, "NLK_MTY")    \
   X(match_wg8, "NLK_MATCH_WG8") X(match_bx2, "NLK_MATCH_BX2") X(match_block, "NLK_MATCH_BLOCK")              \
   X(match_noblock, "NLK_MATCH_NOBLOCK") X(match_order, "NLK_MATCH_ORDER") X(commit_wave, "NLK_COMMIT_WAVE")    \
   X(commit_band, "NLK_COMMIT_BAND") X(no_chase, "NLK_NO_CHASE") X(chase_test_skip0, "NLK_CHASE_TEST_SKIP0") X(bands, "NLK_BANDS") X(host_bands, "NLK_HOST_BANDS")                    \
@@ -216,7 +216,7 @@ static inline bool nlk_packed_geom(const NlkGeom& g) {
 // decisions of the view's rows
 typedef int NlkGroupLauncher(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float* img, const float* cur,
                              const float* prev, float* acc, const uint8_t* active);
-// tu_group8.hip: the matrix-core / register group kernels for 8x8 patches
+// tu_group8.hip: the matrix-core group kernel for 8x8 patches
 NlkGroupLauncher nlk_launch_group8;
 // tu_groupp_{a,b,c}.hip: the packed-lane kernel (k_groupp.h), patch sizes 2..8 / 9..12 / 13..16, any channel count
 NlkGroupLauncher nlk_launch_groupp_a, nlk_launch_groupp_b, nlk_launch_groupp_c;

@@ -30,7 +30,7 @@ int launch_group(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float*
   // Default: 8x8 patches with 1 or 3 channels on the matrix cores (k_group8m.h: 1.04 ms at C2 against
   // 1.34 ms for the packed-lane kernel), everything else on the packed-lane kernel (k_groupp.h; its
   // per-lane candidate lists hold up to 128 entries). Comparison variants: NLK_GROUP_PACKED=1 (8x8 on
-  // k_groupp), NLK_GROUP_DPP=1 (8x8: registers + DPP), NLK_GENERIC_GROUP=1 (LDS-DCT kernel). Lists of more than 128
+  // k_groupp), NLK_GENERIC_GROUP=1 (LDS-DCT kernel). Lists of more than 128
   // entries (capacity k or group size) go to the LDS-DCT kernel (k_group_lds.h): its fixed shapes where they are
   // instantiated (nlk_fixed_shape) and its run-time shape (patch size and channel count from NlkGeom) otherwise, as
   // patches above 16 do
@@ -391,7 +391,7 @@ static bool chase_selected(const nlk_ctx* c, const NlkGeom& g) {
   return g.R >= 1 && g.R <= 3 && g.ngx <= 2048 && g.psz == 8 && (g.ch == 1 || g.ch == 3) && g.kmax <= 128 && g.gstride <= 128 &&
          !c->deterministic && c->planes.cap < ((size_t)1 << 32) && !nlk_set(c->sw.no_chase) &&
          !nlk_set(c->sw.commit_wave) && !nlk_set(c->sw.commit_band) &&
-         !nlk_set(c->sw.generic_group) && !nlk_set(c->sw.group_packed) && !nlk_set(c->sw.group_dpp);
+         !nlk_set(c->sw.generic_group) && !nlk_set(c->sw.group_packed);
 }
 
 // phase 3 for the target rows [r0, r0 + rows) of the last plan (c->last); `chase`: the mask replay the launch is

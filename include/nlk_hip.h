@@ -102,14 +102,14 @@ int nlk_ctx_reload_switches(nlk_ctx *ctx);
 /* What the context's last group launch ran - a read-only report for tests and tools (a test that forces a tile shape
  * with NLK_GTX / NLK_GTY must see that this shape is what ran). Written after the launch is enqueued; nothing on a
  * launch path reads it. A frame worked in bands or strips reports its last launch.
- *   out[0]  kernel family: NLK_GROUP_FAMILY_OTHER (another launcher ran, or none yet), _8M (k_group8m), _8 (k_group8)
- *   out[1]  DCT form of k_group8m (NLK_GROUP_SEP: 0, 2 or 6; 0 for k_group8)
+ *   out[0]  kernel family: NLK_GROUP_FAMILY_OTHER (another launcher ran, or none yet), _8M (k_group8m)
+ *   out[1]  DCT form of k_group8m (NLK_GROUP_SEP: 0, 2 or 6)
  *   out[2..7]  pass 0: tgx, tgy (targets per tile), ntx, nty (tiles), nty_full (tile rows of tgy grid rows; the
  *              nty - nty_full after them hold one grid row each), single (last grid rows, one target per workgroup)
  *   out[8]  launches (2: deterministic mode's near and far pass of a temporal frame)
  *   out[9]  reach of the mask replay inside the launch (0: the replay is not in the launch)
  *   out[10..11]  far pass: tgx, tgy (0 when there is none) */
-enum { NLK_GROUP_FAMILY_OTHER = 0, NLK_GROUP_FAMILY_8M = 1, NLK_GROUP_FAMILY_8 = 2 };
+enum { NLK_GROUP_FAMILY_OTHER = 0, NLK_GROUP_FAMILY_8M = 1 };
 int nlk_ctx_last_group_shape(nlk_ctx *ctx, int out[12]);
 /* ... and whether that launch was k_group8m's packed-list instantiation, which reads a tile's candidate and member
  * lists as one word per lane (csrc/nlk_common.h; NLK_PACKED_LISTS=0 keeps the 32-bit lists): bit 0 = pass 0,

@@ -2,7 +2,7 @@
 10-bit and negative levels, a unit range, betas from 0 to 10.
 
 k_group8m and k_groupp form their variances from sums, (T[1] - T[0] * T[0] * in1) * in1, made safe by a pivot (the
-target patch's coefficient is subtracted first); k_group8 and k_group_lds run the oracle's Welford recursion. At sigma
+target patch's coefficient is subtracted first); k_group_lds runs the oracle's Welford recursion. At sigma
 20 / level 128 a float32 variance from sums WITHOUT the pivot is wrong by 3e-4, which no pixel test sees; at sigma 1 /
 level 245 by 50 %, at sigma 2 / level 1000 by 200 %. Every regime below runs the four frame calls (FLT1 spatial, FLT1
 temporal, FLT2, SMO1) of one noisy pair
@@ -66,7 +66,6 @@ VARIANTS = {
     "sep2": ({"NLK_GROUP_SEP": "2"}, "k_group8m", 2),
     "sep6": ({"NLK_GROUP_SEP": "6"}, "k_group8m", 6),
     "ilp0": ({"NLK_GROUP_ILP": "0"}, "k_group8m", None),
-    "dpp": ({"NLK_GROUP_DPP": "1"}, "k_group8", 0),
     "packed": ({"NLK_GROUP_PACKED": "1"}, None, None),
     "generic": ({"NLK_GENERIC_GROUP": "1"}, None, None),
 }
@@ -231,7 +230,7 @@ def _check_regime(ctx, built, O, monkeypatch, name, variant):
 @pytest.mark.parametrize("name", REGIMES_8X8)
 @pytest.mark.parametrize("variant", list(VARIANTS))
 def test_group_kernel_variants_by_regime(ctx, built, O, monkeypatch, variant, name):
-    """Every 8 x 8 group kernel - k_group8m by default, in each DCT form and under the default scheduler, k_group8,
+    """Every 8 x 8 group kernel - k_group8m by default, in each DCT form and under the default scheduler,
     k_groupp<8>, k_group_lds - on every 8 x 8 regime: (a) integer records exact against the oracle; (b) pixels within
     the scaled 2e-3 / 2e-4 of the float64 restatement, no pixel excused; (c) the weight plane frame_accumulate leaves
     within 16 Y of the restatement's float64 `aggr`, Y being the oracle's own distance from it; (d) with beta_t = 0
@@ -240,7 +239,7 @@ def test_group_kernel_variants_by_regime(ctx, built, O, monkeypatch, variant, na
 
     Largest measured weight deviation as a multiple of Y, per kernel (MI355X, one run; 16 allowed): k_group8m 3.22
     by default, in the separable form and under the default scheduler (level -500, FLT2), 2.25 / 2.26 in the Kronecker /
-    hybrid form; k_group8 2.33; k_groupp<8> 1.44; k_group_lds 1.95. Largest pixel difference as a share of the scaled
+    hybrid form; k_groupp<8> 1.44; k_group_lds 1.95. Largest pixel difference as a share of the scaled
     bar: 0.22 (sigma 5, FLT1 temporal, hybrid form). Nothing grows with the level: no cancellation.
 
     Sensitivity (not committed): with k_groupp's v1 / v0 formed from the sums as they would be WITHOUT the pivot

@@ -843,9 +843,9 @@ def test_smoother_with_a_basic_estimate(ctx, built, O, synth):
         cases.assert_close(g, r, f"smoother with basic {w}x{h}x{ch}")
 
 
-def test_group_kernels_agree_matrix_vs_dpp(ctx, built, synth, monkeypatch):
+def test_group_kernels_agree_matrix_vs_packed_lane(ctx, built, synth, monkeypatch):
     """The 8x8 group kernel has two implementations: k_group8m (DCTs on the f32
-    matrix cores, the default) and k_group8 (registers + DPP, NLK_GROUP_DPP=1).
+    matrix cores, the default) and k_groupp<8> (packed lanes, NLK_GROUP_PACKED=1).
     Same records, same formulas, different summation orders: all four frame calls
     must agree to FP noise (and neither is a fallback of the other: both run HIP)."""
     w, h, ch, sigma = 320, 200, 3, 20.0
@@ -862,13 +862,13 @@ def test_group_kernels_agree_matrix_vs_dpp(ctx, built, synth, monkeypatch):
         s0, _ = _dev_frame(ctx, True, f0, f2, None, sigma, p3)
         return f0, f1, f2, s0
 
-    monkeypatch.delenv("NLK_GROUP_DPP", raising=False)
+    monkeypatch.delenv("NLK_GROUP_PACKED", raising=False)
     a = chain()
-    monkeypatch.setenv("NLK_GROUP_DPP", "1")
+    monkeypatch.setenv("NLK_GROUP_PACKED", "1")
     b = chain()
     for name, x, y in zip(("flt1 spatial", "flt1 temporal", "flt2", "smo1"), a, b):
         assert np.isfinite(x).all() and np.isfinite(y).all()
-        cases.assert_close(x, y, f"matrix vs DPP group kernel, {name}")
+        cases.assert_close(x, y, f"matrix vs packed-lane group kernel, {name}")
 
 
 def test_4k_patch12_against_parallel_oracle(ctx, built, O, synth):

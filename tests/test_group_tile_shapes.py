@@ -1,6 +1,6 @@
 """The tile shapes a full-size frame gives the 8 x 8 group kernels, on frames small enough for the serial oracle.
 
-The launcher (csrc/tu_group8.hip, shape()) picks the targets per tile from the size of the patch grid: 3 x 2 with
+The launcher (csrc/tu_group8.hip, shape_pass()) picks the targets per tile from the size of the patch grid: 3 x 2 with
 one-row "tail" tiles and "single" targets at the end of a 1080p temporal frame, 2 x 2 / 3 x 2 for its first frame,
 2 x 1 at 720p - and 1 x 1 for everything a quick test can afford. Here NLK_GTX / NLK_GTY / NLK_G8_TAIL /
 NLK_G8_SINGLE force those shapes onto grids of a few hundred targets, and Context.last_group_shape() says what the
@@ -414,27 +414,29 @@ def test_deterministic_mode_over_multi_target_tiles(det_ctx, built, O, monkeypat
             _against_oracle(a, rec, call, what, flips=0)
 
 
-# ---------------------------------------------------------------- (h) k_group8 (registers + DPP)
-
-@pytest.mark.parametrize("shape", [(3, 1), (2, 2), (3, 2)], ids=lambda s: f"{s[0]}x{s[1]}")
-def test_dpp_kernel_over_multi_target_tiles(ctx, built, O, monkeypatch, shape):
-    """k_group8 (NLK_GROUP_DPP=1) reads the same tgx / tgy as the matrix-core kernel, in uniform tiles: the four frame
-    calls, one and three channels, against the oracle."""
+def test_deterministic_mode_on_the_packed_lane_kernel(det_ctx, built, O, monkeypatch):
+    """Deterministic aggregation under NLK_GROUP_PACKED=1: k_groupp<8>, one target per tile, whose launcher takes its
+    slabs, flags and counters from the same plan as k_group8m's (csrc/group_det.h) - a temporal frame's near and far
+    pass each sized by its own tiles. Two runs bit for bit the same, and the oracle's frame without a single excused
+    sample beyond the threshold pixels, as the matrix-core kernel gives on this scene."""
     w, h = FRAME_A
-    ngx, ngy = _grid(w, h)
-    monkeypatch.setenv("NLK_GROUP_DPP", "1")
-    _force(monkeypatch, *shape)
+    monkeypatch.setenv("NLK_GROUP_PACKED", "1")
     for ch in (3, 1):
         scene = _scene(O, built, w, h, ch)
-        for name in CALLS:
-            what = f"k_group8, {shape[0]} x {shape[1]} tiles, {ch} ch, {name}"
-            g, rec = _run(ctx, scene[name])
-            s = _assert_ran(ctx, ngx, ngy, *shape, family="k_group8", what=what)
-            assert s["chase"] == 0 and s["passes"] == 1, f"{what}: {s}"
-            _against_oracle(g, rec, scene[name], what)
+        for name in ("flt1 temporal", "flt1 spatial", "smo1"):
+            call = scene[name]
+            what = f"deterministic, k_groupp<8>, {ch} ch, {name}"
+            p = call[2]
+            assert p.search_sz_x > p.search_sz_t or name == "smo1"
+            a, rec = _run(det_ctx, call)
+            # (this launcher reports no shape, so the two passes of "flt1 temporal" follow from the radii above alone)
+            assert det_ctx.last_group_shape()["family"] is None, what
+            b, _ = _run(det_ctx, call)
+            assert np.array_equal(a, b, equal_nan=True), f"{what}: two runs differ"
+            _against_oracle(a, rec, call, what, flips=0)
 
 
-# ---------------------------------------------------------------- (i) random parameters at 8 x 8
+# ---------------------------------------------------------------- (h) random parameters at 8 x 8
 
 _RANDOM_SHAPES = [(3, 2), (2, 2), (2, 3), (4, 1)]
 

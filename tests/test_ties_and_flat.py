@@ -406,6 +406,8 @@ def test_ties_patch_20_on_the_lds_dct_route(ctx, built, O):
 ZEROVAR = {"flat-gray": ("flat", 48, 40, 1, 0, 0), "flat-rgb": ("flat", 48, 40, 3, 0, 0),
            "clip-gray": ("clip", 48, 40, 1, 0, 71), "clip-rgb": ("clip", 48, 40, 3, 0, 72),
            "tiled-gray": ("tiled", 48, 40, 1, 4, 73), "tiled-rgb": ("tiled", 48, 40, 3, 2, 74)}
+# ("dpp": NLK_GROUP_DPP selected the retired k_group8 and is ignored like any unknown variable now: these cases hold the
+# default kernel to the same checks with it set)
 GROUP_KERNELS = {"default": {}, "sep0": {"NLK_GROUP_SEP": "0"}, "sep2": {"NLK_GROUP_SEP": "2"},
                  "sep6": {"NLK_GROUP_SEP": "6"}, "dpp": {"NLK_GROUP_DPP": "1"}, "lds-dct": {"NLK_GENERIC_GROUP": "1"}}
 ZV_NAMES = ("flt1x", "flt1t", "flt2", "flt2x")
