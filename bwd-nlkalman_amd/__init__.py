@@ -30,7 +30,7 @@ HIP_SYMBOLS = [
     "nlk_dev_strip_match", "nlk_dev_strip_match_rows", "nlk_dev_mask_commit", "nlk_dev_strip_group",
     "nlk_tvl1_default_params", "nlk_tvl1_scales", "nlk_dev_tvl1_flow", "nlk_dev_gray",
     "nlk_dev_occlusion_mask", "nlk_dev_image_dct", "nlk_dev_copy_block", "nlk_host_tables", "nlk_ctx_set_deterministic", "nlk_dev_zero", "nlk_dev_add", "nlk_dev_copy_peer",
-    "nlk_filter_frame_host", "nlk_smooth_frame_host", "nlk_dev_strip_match_part", "nlk_ctx_reload_switches", "nlk_ctx_last_group_shape", "nlk_ctx_last_group_packed", "nlk_host_packed_entry", "nlk_ctx_count_packed", "nlk_ctx_set_strip_accumulator",
+    "nlk_filter_frame_host", "nlk_smooth_frame_host", "nlk_dev_strip_match_part", "nlk_ctx_reload_switches", "nlk_ctx_last_group_shape", "nlk_ctx_last_group_packed", "nlk_host_packed_entry", "nlk_host_match_plan", "nlk_ctx_count_packed", "nlk_ctx_set_strip_accumulator",
     "nlk_strips_create", "nlk_strips_destroy", "nlk_strips_last_error", "nlk_rccl_unique_id", "nlk_strips_rccl_init",
     "nlk_strips_transport", "nlk_strips_load", "nlk_strips_set_options", "nlk_strips_step", "nlk_strips_sync",
     "nlk_strips_own_rows", "nlk_strips_ctx", "nlk_strips_geometry", "nlk_strips_stats", "nlk_strips_set_dry_run",
@@ -261,6 +261,7 @@ def hip():
         L.nlk_ctx_last_group_shape.argtypes = [vp, C.POINTER(i)]
         L.nlk_ctx_last_group_packed.argtypes = [vp]
         L.nlk_host_packed_entry.argtypes = [i, i, i, i, i, i, i, C.POINTER(C.c_uint), C.POINTER(i)]
+        L.nlk_host_match_plan.argtypes = [i, i, i, C.POINTER(Params), i, i, i, C.POINTER(i)]
         L.nlk_ctx_count_packed.argtypes = [vp, C.POINTER(i)]
         L.nlk_ctx_set_strip_accumulator.argtypes = [vp, vp]
         L.nlk_strips_create.argtypes = [C.POINTER(vp), i, C.POINTER(i), i, i, i, i, i, C.c_float, C.POINTER(Params), i, i]
@@ -506,6 +507,21 @@ def host_packed_entry(dx, dy, r, k=1, px=16, py=16, passthrough=False):
     if hip().nlk_host_packed_entry(px, py, dx, dy, r, k, int(passthrough), C.byref(byte), back):
         return None
     return byte.value, (back[0], back[1])
+
+
+MATCH_PLAN_FIELDS = ("generic", "wide", "tgx", "tgy", "bx", "threads", "block", "order", "halo", "rwp", "rh_max",
+                     "ksel_max", "ntx", "rounds", "lds", "wide_halo", "wide_rwp", "wide_rh_max", "wide_rounds", "wide_lds")
+
+
+def host_match_plan(w, h, ch, params, smoother=False, have_prev=False, rows=0):
+    """The launch plan of a frame call's block matching as a dict of MATCH_PLAN_FIELDS (nlk_host_match_plan: the frame
+    call's geometry code and planner, the NLK_* switches from the environment; no device needed). rows: the call's
+    target rows, 0 = the whole grid. NlkError, whose args[1] is the frame call's error code, for refused inputs."""
+    out = (C.c_int * len(MATCH_PLAN_FIELDS))()
+    rc = hip().nlk_host_match_plan(int(w), int(h), int(ch), C.byref(params), int(smoother), int(have_prev), int(rows), out)
+    if rc:
+        raise NlkError(hip().nlk_last_error(None).decode(), rc)
+    return dict(zip(MATCH_PLAN_FIELDS, out))
 
 
 def reload_switches():

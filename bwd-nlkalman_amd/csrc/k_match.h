@@ -34,18 +34,7 @@
 #endif
 #define NLK_BM_WAVES (NLK_BM_THREADS / 64)
 
-struct NlkTile {
-  int tgx, tgy;       // targets per tile
-  int bx;             // targets per block along x: 4, or 2 (k_bm_topk<.., 2>: 12 x 12 patches, 8 wavefronts on an 8 x 4 tile)
-  int ntx, nty;       // tiles
-  int rwp, rh_max;    // LDS region: padded row stride (floats) / rows
-  int ksel_max;       // capacity of the per-wave survivor arrays
-  int halo;           // search halo held in LDS (windows reaching further read HBM/L2)
-  int block;          // 4 x 2-target blocks share their squared differences (0: NLK_MATCH_NOBLOCK, target by target)
-  int threads;        // k_bm_topk: threads per workgroup (256, or 512 for tiles of 8 x 8 targets)
-  int order;          // summation order of the distances: 0 = the reference's (exact), 1 = block-summed (opt-in; 8 x 8 patches)
-  int packed;         // != 0: the targets' packed lists (nlk_common.h) are written and flagged
-};
+// (NlkTile, the launch shape both kernels take: nlk_common.h)
 
 // OR over the 64 lanes, in every lane. (Round 6: four DPP steps inside the rows of 16 lanes and the two row-swap
 // instructions instead of six ds_bpermute round trips per half word - no LDS instruction, no LDS latency in the
@@ -503,6 +492,19 @@ __device__ __forceinline__ void nlk_match_epilogue(const NlkGeom& g, size_t t, i
 #ifndef NLK_BM7_WAVES
 #define NLK_BM7_WAVES 4
 #endif
+// The rounds classes k_bm_topk / k_bm_wide are instantiated for (MAXM: rounds of 64 candidates a window may take), and
+// which of them have blocks of 2 x 2 targets (k_bm_topk<.., BX = 2, ..>: 2 rounds from 8 x 8 patches on, and the seven
+// rounds of a first frame's 441 candidates at 8 x 8). THE statement of both: the planner (tu_match.hip) asks at run
+// time, the launcher (match_launch.h) in its `if constexpr`.
+constexpr int nlk_bm_rounds_class(int rounds) { return rounds <= 2 ? 2 : (rounds <= 7 ? 7 : 16); }
+constexpr bool nlk_bm_has_bx2(int psz, int maxm) { return psz >= 8 && (maxm == 2 || (maxm == 7 && psz == 8)); }
+
+// Dynamic LDS bytes of a k_bm_topk launch: the carve-up at the head of the kernel (tile, then per wavefront the 64-bit
+// survivors, the kept candidates and the group), with one float more than the tile where the kernel rounds the tile up
+// to an even count. (The kernel's own pointer lines do not call this: they were left as they are.)
+static inline size_t nlk_bm_topk_lds(const NlkTile& tl, int ch, int gstride) {
+  return sizeof(float) * ((size_t)ch * tl.rwp * tl.rh_max + 1 + (size_t)(tl.threads / 64) * (3 * tl.ksel_max + gstride));
+}
 // ORD: 0 = the reference's (hy, hx, c) summation order (bit-identical distances), 1 = block-summed (opt-in, above)
 template <int PSZ, int CH, int MAXM, int BX = 4, int ORD = 0>  // BX x 2 targets per block (2: twice the wavefronts on the same tile)
 __global__ void __launch_bounds__(512, MAXM == 7 ? (BX == 2 ? NLK_BM7_WAVES : 3) : ((MAXM == 2 && PSZ == 8) ? 8 : 2))  // (7 rounds in blocks: 168 registers, the LDS tile allows 3 wavefronts per SIMD)
@@ -513,7 +515,7 @@ k_bm_topk(const float* __restrict__ img, const uint8_t* __restrict__ vmap, NlkGe
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // scalar: makes per-target addresses uniform
-  const int nwaves = (int)(blockDim.x >> 6);  // 4, or 8 for tiles of 8 x 8 targets (NlkTile::threads)
+  const int nwaves = (int)(blockDim.x >> 6);  // 4, or 8 with blocks of 2 x 2 targets (NlkTile::threads)
   const int tile_id = nlk_xcd_tile(blockIdx.x, tl.ntx * tl.nty);
   if (tile_id >= tl.ntx * tl.nty) return;
   // Tiles on the image border are the slow ones: the blocks whose windows are clipped go target by target
@@ -725,6 +727,12 @@ k_bm_topk(const float* __restrict__ img, const uint8_t* __restrict__ vmap, NlkGe
 // Targets whose window does not fit the tile of k_bm_topk (queued there): one
 // wavefront per target stages the target's own window (patch + 2*wsz) in a
 // private LDS region and runs the same distance / selection / epilogue code.
+// Dynamic LDS bytes of a k_bm_wide launch: NLK_BM_WAVES times the kernel's per_wave (below; its lines do not call this)
+static inline size_t nlk_bm_wide_lds(const NlkTile& tw, int ch, int gstride) {
+  const size_t per_wave = (((size_t)ch * tw.rwp * tw.rh_max + 1) & ~(size_t)1) +
+                          ((3 * (size_t)tw.ksel_max + gstride + 1) & ~(size_t)1);
+  return sizeof(float) * NLK_BM_WAVES * per_wave;
+}
 template <int PSZ, int CH, int MAXM, int ORD = 0>
 __global__ void __launch_bounds__(NLK_BM_THREADS)
 k_bm_wide(const float* __restrict__ img, const uint8_t* __restrict__ vmap, NlkGeom g, NlkTile tl,

@@ -1,18 +1,19 @@
 // match_launch.h — host-side launcher of k_bm_topk / k_bm_wide for one patch size (included by the
 // tu_match_*.hip units, each of which instantiates a range of patch sizes so that `make -j` compiles them side
-// by side: one unit with all six sizes took 3.5 minutes)
+// by side: one unit with all six sizes took 3.5 minutes). It launches the tile it is given (nlk_match_plan,
+// tu_match.hip); the rounds classes and which of them have 2 x 2 blocks are k_match.h's (nlk_bm_rounds_class,
+// nlk_bm_has_bx2), which the plan asks too.
 #pragma once
 #include "k_match.h"
 #include "nlk_internal.h"
 
 namespace {
 
-
 template <int PSZ, int CH, int MAXM, int ORD>
 int launch_match_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const NlkTile& tl, size_t lds,
                    const float* img, bool wide) {
   auto kern = wide ? k_bm_wide<PSZ, CH, MAXM, ORD> : k_bm_topk<PSZ, CH, MAXM, 4, ORD>;
-  if constexpr (PSZ >= 8 && (MAXM == 2 || (MAXM == 7 && PSZ == 8)))
+  if constexpr (nlk_bm_has_bx2(PSZ, MAXM))
     if (!wide && tl.bx == 2) kern = k_bm_topk<PSZ, CH, MAXM, 2, ORD>;
   HIPCHK(c, hipFuncSetAttribute((const void*)kern,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -29,11 +30,12 @@ int launch_match_t(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const NlkT
 template <int PSZ, int CH, int ORD>
 int launch_match_m(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const NlkTile& tl, size_t lds,
                    const float* img, int maxm, bool wide) {
-  if (maxm <= 2) return launch_match_t<PSZ, CH, 2, ORD>(c, v, g, tl, lds, img, wide);
-  if (maxm <= 7) return launch_match_t<PSZ, CH, 7, ORD>(c, v, g, tl, lds, img, wide);
-  return launch_match_t<PSZ, CH, 16, ORD>(c, v, g, tl, lds, img, wide);
+  switch (nlk_bm_rounds_class(maxm)) {
+    case 2: return launch_match_t<PSZ, CH, 2, ORD>(c, v, g, tl, lds, img, wide);
+    case 7: return launch_match_t<PSZ, CH, 7, ORD>(c, v, g, tl, lds, img, wide);
+    default: return launch_match_t<PSZ, CH, 16, ORD>(c, v, g, tl, lds, img, wide);
+  }
 }
-
 
 template <int PSZ, int ORD = 0>
 int launch_match_psz(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const NlkTile& tl, size_t lds, const float* img,

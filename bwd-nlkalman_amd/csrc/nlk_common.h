@@ -18,6 +18,21 @@ struct NlkGeom {
   float sigma2, beta_x, beta_t;
 };
 
+// Launch shape of a tiled block-matching kernel (k_match.h), passed by value beside NlkGeom; planned by
+// nlk_match_plan (tu_match.hip)
+struct NlkTile {
+  int tgx, tgy;       // targets per tile
+  int bx;             // targets per block along x: 4, or 2 (k_bm_topk<.., 2>: 12 x 12 patches, 8 wavefronts on an 8 x 4 tile)
+  int ntx, nty;       // tiles
+  int rwp, rh_max;    // LDS region: padded row stride (floats) / rows
+  int ksel_max;       // capacity of the per-wave survivor arrays
+  int halo;           // search halo held in LDS (windows reaching further read HBM/L2)
+  int block;          // 4 x 2-target blocks share their squared differences (0: NLK_MATCH_NOBLOCK, target by target)
+  int threads;        // k_bm_topk: threads per workgroup (256, or 512: 8 wavefronts with a block of 2 x 2 targets each)
+  int order;          // summation order of the distances: 0 = the reference's (exact), 1 = block-summed (opt-in; 8 x 8 patches)
+  int packed;         // != 0: the targets' packed lists (below) are written and flagged
+};
+
 // per-target record written by the matching kernel
 struct NlkTarget {
   int nsel;   // number of kept candidates (0: nothing to do)

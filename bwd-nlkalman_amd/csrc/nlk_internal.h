@@ -13,7 +13,6 @@
 #include "nlk_common.h"
 
 struct NlkTvMail;   // k_tvl1.h
-struct NlkTile;     // k_match.h
 struct NlkGTile;    // k_group_tile.h
 
 struct NlkBuf {
@@ -52,7 +51,7 @@ struct NlkRecView {
 #define NLK_SWITCH_LIST(X)                                                                                   \
   X(deterministic, "NLK_DETERMINISTIC") X(generic_group, "NLK_GENERIC_GROUP") X(group_packed, "NLK_GROUP_PACKED") \
   X(group_sep, "NLK_GROUP_SEP") X(group_ilp, "NLK_GROUP_ILP") X(generic_match, "NLK_GENERIC_MATCH") X(mtx, "NLK_MTX") X(mty, "NLK_MTY")    \
-  X(match_wg8, "NLK_MATCH_WG8") X(match_bx2, "NLK_MATCH_BX2") X(match_block, "NLK_MATCH_BLOCK")              \
+  X(match_bx2, "NLK_MATCH_BX2") X(match_block, "NLK_MATCH_BLOCK")              \
   X(match_noblock, "NLK_MATCH_NOBLOCK") X(match_order, "NLK_MATCH_ORDER") X(commit_wave, "NLK_COMMIT_WAVE")    \
   X(commit_band, "NLK_COMMIT_BAND") X(no_chase, "NLK_NO_CHASE") X(chase_test_skip0, "NLK_CHASE_TEST_SKIP0") X(bands, "NLK_BANDS") X(host_bands, "NLK_HOST_BANDS")                    \
   X(host_trace, "NLK_HOST_TRACE") X(gtx, "NLK_GTX") X(gty, "NLK_GTY") X(g8_tail, "NLK_G8_TAIL")              \
@@ -223,10 +222,22 @@ NlkGroupLauncher nlk_launch_groupp_a, nlk_launch_groupp_b, nlk_launch_groupp_c;
 // tu_group_generic.hip: the LDS-DCT kernel (k_group_lds.h), candidate lists of any length: its fixed shapes
 // (nlk_fixed_shape) and its run-time shape: patch sizes up to 32, any channel count with ch * psz^2 <= 4096
 NlkGroupLauncher nlk_launch_group_generic, nlk_launch_group_any;
-// tu_match.hip: block matching + selection (wide = the queued targets of a temporal frame)
-int nlk_launch_match(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const NlkTile& tl, size_t lds, const float* img,
-                     int maxm, bool wide);
-int nlk_launch_match_generic(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const float* img);
+// tu_match.hip: block matching + selection. The plan of a call's match launches, a plain function of its geometry and
+// the switches (no context, no HIP call, no allocation; nlk_host_match_plan shows it to the tests): the tiled kernels'
+// launch shapes for the dominant window and, in a temporal frame whose spatial radius is the larger, for the queued
+// targets' wide window (nty is the launcher's: it depends on the rows it is given), or the generic kernel
+struct NlkMatchPlan {
+  NlkTile tl{}, tw{};            // match tiles: dominant window / wide window
+  size_t lds = 0, lds_w = 0;     // their dynamic LDS bytes
+  int maxm = 0, maxm_w = 0;      // rounds of 64 candidates their windows take
+  bool wide = false;             // the second launch exists (k_bm_wide over the queue)
+  bool generic = false;          // k_bm_generic instead of the tiled kernels
+};
+int nlk_match_plan(const NlkGeom& g, const NlkSwitches& sw, NlkMatchPlan* mp);
+// ... and its launches for the target rows of the view (`g`: their geometry) on the view's stream: the generic kernel,
+// or the dominant launch and then the wide one, whose queue length is cleared first where `clear_queue` asks for it
+int nlk_launch_match(nlk_ctx* c, const NlkRecView& v, const NlkGeom& g, const NlkMatchPlan& mp, bool clear_queue,
+                     const float* img);
 // tu_commit.hip: the replay of the processed mask (k_commit.h) over the mark words of the grid rows
 // [first, first + nrows); `marks` / `active` = whole-grid arrays, the decisions of the rows before `first` are final in
 // `active`; `total` = rows of the whole grid when it is replayed band by band (first > 0 continues the band before).
@@ -253,3 +264,9 @@ int check_images(nlk_ctx* c, const void* out, const void* cur, int w, int h, int
 // the orthonormal DCT-II basis [n][n] and the aggregation window [psz][psz] a frame call uploads (nlk_host_tables)
 void host_basis(float* C, int n);
 void host_window(float* W, int psz);
+
+// ---- tu_frame.hip, for nlk_host_match_plan (tu_match.hip)
+// The geometry of a frame or strip call from its arguments and nlk_frame_grid, with the checks a frame call makes
+// behind its opening one (check_images), in its order, with its codes and messages. Host only; `c` may be null.
+int nlk_frame_geom(nlk_ctx* c, NlkGeom& g, int w, int h, int ch, float sigma, const struct nlkalman_params* P, int oy,
+                   int ngy, int smoother, bool have_prev, bool have_basic);

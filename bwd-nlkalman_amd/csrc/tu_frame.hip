@@ -1,12 +1,11 @@
 // tu_frame.hip — the frame pipeline behind the frame calls of include/nlk_hip.h: the plan of a frame or strip call
-// (geometry from nlk_frame_grid, planar images, scratch, match tiles), its phases (layout, block matching, mask replay,
+// (geometry from nlk_frame_grid, planar images, scratch; the match launches are planned by tu_match.hip), its phases (layout, block matching, mask replay,
 // groups, normalisation) as whole-frame calls, as the strip entry points and as the host-pointer calls that move the
 // frame in row bands, the profiling events the phases record, and the readers of a call's records. The kernels of the
 // phases live in their own units (nlk_internal.h: the launchers); this one compiles k_frame.h.
 #include <time.h>
 
 #include "k_frame.h"
-#include "k_match.h"   // NlkTile (the kernels themselves are compiled in tu_match.hip)
 #include "nlk_internal.h"
 
 namespace {
@@ -77,6 +76,40 @@ void mark(nlk_ctx* c, int i) {
 
 }  // namespace
 
+// The geometry of a frame or strip call (nlk_internal.h): plan_frame's, and nlk_host_match_plan's
+int nlk_frame_geom(nlk_ctx* c, NlkGeom& g, int w, int h, int ch, float sigma, const struct nlkalman_params* P, int oy,
+                   int ngy, int smoother, bool have_prev, bool have_basic) {
+  g.w = w; g.h = h; g.ch = ch;
+  g.psz = P->patch_sz;
+  if (g.psz < 2 || g.psz > 32 || ch * g.psz * g.psz > 4096)
+    return fail(c, NLK_EUNSUP, "patch size %d with %d channels not supported (2..32, ch * psz^2 <= 4096)", g.psz, ch);
+  g.p2 = g.psz * g.psz;
+  g.E = g.p2 * ch;
+  struct nlk_frame_grid fg;
+  if (nlk_frame_grid(w, h, P, smoother, have_prev, &fg)) return fail(c, NLK_EINVAL, "image smaller than a patch");
+  g.step = fg.step;
+  g.ngx = fg.ngx;
+  g.oy = oy;
+  g.ngy = ngy;
+  if (oy < 0 || ngy < 1 || oy + (ngy - 1) * g.step + g.psz > h)
+    return fail(c, NLK_EINVAL, "target rows [%d + j*%d, j < %d) leave the %d-row strip", oy,
+                g.step, ngy, h);
+  g.wsz_x = P->search_sz_x; g.wsz_t = P->search_sz_t;
+  g.npx = P->npatches_x; g.npt = P->npatches_t; g.ntagg = P->npatches_tagg;
+  if (g.wsz_x < 0 || g.wsz_t < 0 || g.ntagg < 0)
+    return fail(c, NLK_EINVAL, "negative search radius or group size (call nlkalman_default_params first)");
+  g.have_prev = have_prev;
+  g.have_basic = have_basic;
+  g.smoother = smoother != 0;
+  g.sigma2 = sigma * sigma;
+  g.beta_x = P->beta_x; g.beta_t = P->beta_t;
+  // reach (in grid cells) of the groups that mark the processed-mask
+  g.R = fg.reach;  // (R > 3: the mask replay runs from the coordinate lists, tu_commit.hip)
+  g.kmax = max(max(g.npx, g.npt), 1);
+  g.gstride = max(g.ntagg, 1);
+  return NLK_OK;
+}
+
 extern "C" {
 
 int nlk_ctx_set_profiling(nlk_ctx* c, int on) {
@@ -131,17 +164,13 @@ int nlk_ctx_last_group_packed(nlk_ctx* c) {
   return c->group_packed;
 }
 
-// ---- frame plan: geometry, planar images, scratch and the launch shapes of one frame or strip call
+// ---- frame plan: geometry, planar images, scratch and the match plan of one frame or strip call
 struct NlkPlan {
   NlkGeom g{};                   // the whole call: target rows [0, g.ngy) from image row g.oy
   const float *img_cur = nullptr, *img_prev = nullptr, *img_basic = nullptr, *img_match = nullptr;
   const float* img_diff = nullptr;   // smoother calls: planar prev - cur
-  NlkTile tl{}, tw{};            // match tiles: dominant window / wide window
-  size_t lds = 0, lds_w = 0;
-  int maxm = 0, maxm_w = 0;
-  bool wide = false;
+  NlkMatchPlan mp;               // the launches of the block matching (tu_match.hip)
   bool wide0_zeroed = false;     // the layout kernel has cleared the queue length of band 0 (rows from 0)
-  bool generic = false;          // k_bm_generic instead of the tiled kernels
 };
 
 // records of the target rows from `r0` on (a view into the call's buffers; `marks_ext`: the mark words go to the
@@ -203,42 +232,9 @@ static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* pr
   NLK_USE_DEVICE(c);
   nlk_set_lazy_active(c, 0, 0, nullptr);  // (whatever replays this call's mask: `active` holds its bytes unless set again)
   NlkGeom& g = pl.g;
-  g.w = w; g.h = h; g.ch = ch;
-  g.psz = P->patch_sz;
-  if (g.psz < 2 || g.psz > 32 || ch * g.psz * g.psz > 4096)
-    return fail(c, NLK_EUNSUP, "patch size %d with %d channels not supported (2..32, ch * psz^2 <= 4096)", g.psz, ch);
-  g.p2 = g.psz * g.psz;
-  g.E = g.p2 * ch;
-  struct nlk_frame_grid fg;
-  if (nlk_frame_grid(w, h, P, smoother, prev != nullptr, &fg)) return fail(c, NLK_EINVAL, "image smaller than a patch");
-  g.step = fg.step;
-  g.ngx = fg.ngx;
-  g.oy = oy;
-  g.ngy = ngy;
-  if (oy < 0 || ngy < 1 || oy + (ngy - 1) * g.step + g.psz > h)
-    return fail(c, NLK_EINVAL, "target rows [%d + j*%d, j < %d) leave the %d-row strip", oy,
-                g.step, ngy, h);
-  g.wsz_x = P->search_sz_x; g.wsz_t = P->search_sz_t;
-  g.npx = P->npatches_x; g.npt = P->npatches_t; g.ntagg = P->npatches_tagg;
-  if (g.wsz_x < 0 || g.wsz_t < 0 || g.ntagg < 0)
-    return fail(c, NLK_EINVAL, "negative search radius or group size (call nlkalman_default_params first)");
-  g.have_prev = prev != nullptr;
-  g.have_basic = basic != nullptr;
-  g.smoother = smoother != 0;
-  g.sigma2 = sigma * sigma;
-  g.beta_x = P->beta_x; g.beta_t = P->beta_t;
-  const int wmax = g.smoother ? g.wsz_t : (g.have_prev ? max(g.wsz_x, g.wsz_t) : g.wsz_x);
-  // reach (in grid cells) of the groups that mark the processed-mask
-  g.R = fg.reach;  // (R > 3: the mask replay runs from the coordinate lists, tu_commit.hip)
-  const int ncand = (2 * wmax + 1) * (2 * wmax + 1);
-  // the tiled matching kernels exist for patch sizes 4 / 6 / 8 / 10 / 12 / 16, 1 or 3 channels and
-  // windows of up to 1024 candidates; everything else the reference accepts goes to k_bm_generic
-  pl.generic = !nlk_fixed_shape(g.psz, ch) || ncand > 64 * 16 || nlk_set(c->sw.generic_match);
-  g.kmax = max(max(g.npx, g.npt), 1);
+  if ((rc = nlk_frame_geom(c, g, w, h, ch, sigma, P, oy, ngy, smoother, prev != nullptr, basic != nullptr))) return rc;
   const int ngrid = g.ngx * g.ngy;
   const int npix = w * h;
-  const int ntagg_alloc = max(g.ntagg, 1);
-  g.gstride = ntagg_alloc;
 
   mark(c, 0);
   // ---- layout: planar copies + the row test of the validity map (+ clearing the accumulator of a
@@ -266,96 +262,19 @@ static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* pr
   if ((rc = upload_tables(c, g.psz))) return rc;
   if ((rc = reserve(c, c->topk, sizeof(uint32_t) * (size_t)ngrid * g.kmax)) ||
       (rc = reserve(c, c->tinfo, sizeof(NlkTarget) * (size_t)ngrid)) ||
-      (rc = reserve(c, c->gcoords, sizeof(uint32_t) * (size_t)ngrid * ntagg_alloc)) ||
+      (rc = reserve(c, c->gcoords, sizeof(uint32_t) * (size_t)ngrid * g.gstride)) ||
       (rc = reserve(c, c->marks, sizeof(uint64_t) * (size_t)ngrid)) ||
       (rc = reserve(c, c->active, (size_t)ngrid)))
     return rc;
   mark(c, 1);
 
-  // ---- launch shapes of the block matching
+  // ---- launch shapes of the block matching (tu_match.hip)
   pl.img_match = basic ? pl.img_basic : pl.img_cur;
-  NlkTile& tl = pl.tl;
-  // 8 x 4 targets per workgroup, four 4 x 2 blocks that share their squared differences. A small grid
-  // (fewer than ~2 such tiles per CU: 256 x 256, 512 x 384, a 34-row strip of a 1080p frame) is latency bound
-  // instead: 4 x 2 tiles, one target at a time, two targets per wavefront (C1: match 0.058 -> 0.02 ms).
-  // Where the two meet (round 4, temporal / first-frame match ms, blocks against target by target): 384 tiles
-  // 0.059 / 0.144 against 0.053 / 0.141; 486: 0.061 / 0.148 against 0.060 / 0.178; 600 (640 x 480): 0.071 / 0.188
-  // against 0.071 / 0.221; 950 (800 x 600): 0.087 / 0.241 against 0.095 / 0.302; 1020 (960 x 540, and the 67-row
-  // strips of four GPUs): 0.085 / 0.249 against 0.101 / 0.330. (Until then the limit was 1024 tiles.)
-  const bool small_grid = (size_t)((g.ngx + 7) / 8) * ((g.ngy + 3) / 4) < 576;
-  tl.tgx = nlk_or(c->sw.mtx, small_grid ? 4 : 8);
-  tl.tgy = nlk_or(c->sw.mty, small_grid ? 2 : 4);
-  // 8 wavefronts per workgroup where the search radius is the temporal one (FLT1 / FLT2 temporal, SMO1), measured at
-  // 1080p, match ms with 8 x 8 patches: 8 x 4 tile, 4 wavefronts, blocks of 4 x 2 targets 0.305 (20 wavefronts per CU);
-  // 8 x 8 tile, 8 wavefronts, 4 x 2 blocks 0.294 (45 KB: three per CU = 24); 8 x 4 tile, 8 wavefronts with a block of
-  // 2 x 2 targets each, 64 registers 0.268 (30 KB: four per CU = 32, a fifth more subtractions and multiplications)
-  // - the default. 10 x 10 patches and more: the same 2 x 2 blocks (4K, 12 x 12: 0.864 -> 0.762, 16 x 16: 1.22 -> 0.91).
-  // With the spatial radius the tiles are too large for more than the four wavefronts (8 x 8 tile 62 KB: 0.95 -> 1.22).
-  // NLK_MATCH_BX2=0 keeps the 4 x 2 blocks, NLK_MATCH_WG8=1 the 8 x 8 tiles.
-  tl.threads = NLK_BM_THREADS;
-  tl.bx = 4;
-  {
-    const int halo0 = (g.smoother || g.have_prev) ? g.wsz_t : g.wsz_x;
-    const bool tiles84 = tl.tgx == 8 && tl.tgy == 4 && (nlk_set(c->sw.match_block) || !small_grid);  // (the tiles of a full-size frame)
-    // (the launcher's own condition, match_launch.h: blocks of 2 x 2 exist for MAXM 2, and for MAXM 7 at 8 x 8)
-    const int rounds0 = ((2 * halo0 + 1) * (2 * halo0 + 1) + 63) / 64;
-    if (nlk_or(c->sw.match_wg8, 0) != 0 && g.psz <= 8 && tiles84) { tl.threads = 512; tl.tgy = 8; }
-    else if (nlk_or(c->sw.match_bx2, 1) != 0 && tiles84 && g.psz >= 8 && (rounds0 <= 2 || (g.psz == 8 && rounds0 <= 7))) {
-      // (... and the seven-round blocks of a first frame, 441 candidates: 2 x 2 targets per block need 128 registers
-      // instead of 168 + spills, two 8-wavefront workgroups per CU instead of three of 4: match 0.947 -> 0.828)
-      tl.threads = 512;
-      tl.bx = 2;
-    }
-  }
-  tl.ntx = (g.ngx + tl.tgx - 1) / tl.tgx;
-  tl.block = nlk_set(c->sw.match_noblock) ? 0 : (nlk_set(c->sw.match_block) ? 1 : !small_grid);
-  // the opt-in block-summed distance order (NLK_MATCH_ORDER=block; 8 x 8 patches, k_bm_topk / k_bm_wide); everything
-  // else - and the default - sums in the reference's order
-  tl.order = (nlk_or(c->sw.match_order, 0) == 1 && g.psz == 8) ? 1 : 0;
-  // LDS holds the halo of the dominant window; its row stride = window width
-  // (mod 32): candidate i of a window then sits on bank i mod 32, so a
-  // wavefront's 64 candidate reads are conflict free
-  tl.halo = (g.smoother || g.have_prev) ? g.wsz_t : g.wsz_x;
-  {
-    const int need = (tl.tgx - 1) * g.step + 2 * tl.halo + g.psz;
-    const int wdom = 2 * tl.halo + 1;
-    tl.rwp = need + ((wdom - need) % 32 + 32) % 32;
-  }
-  tl.rh_max = (tl.tgy - 1) * g.step + 2 * tl.halo + g.psz;
-  tl.ksel_max = g.kmax;
-  auto tile_lds = [&]() {
-    return sizeof(float) * ((size_t)ch * tl.rwp * tl.rh_max + 1 + (size_t)(tl.threads / 64) * (3 * tl.ksel_max + ntagg_alloc));
-  };
-  pl.lds = tile_lds();
-  if (pl.lds > 160 * 1024 && tl.threads > NLK_BM_THREADS && tl.tgy == 4) {
-    // (very long lists: the per-wavefront list space of 8 wavefronts does not fit beside the tile - 4 wavefronts, 4 x 2 blocks)
-    tl.threads = NLK_BM_THREADS;
-    tl.bx = 4;
-    pl.lds = tile_lds();
-  }
-  if (pl.lds > 160 * 1024) pl.generic = true;  // (a k or window too large for the tile: the generic kernel)
-  // targets of a temporal frame without a valid previous patch search the spatial window
-  // (reference: :637); when that one is the wider, they are queued for a second launch
-  pl.wide = !pl.generic && g.have_prev && !g.smoother && g.wsz_x > g.wsz_t;
-  const int wdom = 2 * tl.halo + 1;
-  pl.maxm = (wdom * wdom + 63) / 64;
-  if (pl.wide) {
-    NlkTile& tw = pl.tw;
-    tw = tl;
-    const int need = 2 * g.wsz_x + g.psz, ww = 2 * g.wsz_x + 1;
-    tw.halo = g.wsz_x;
-    tw.rwp = need + ((ww - need) % 32 + 32) % 32;
-    tw.rh_max = need;
-    const size_t per_wave = (((size_t)ch * tw.rwp * tw.rh_max + 1) & ~(size_t)1) +
-                            ((3 * (size_t)tw.ksel_max + ntagg_alloc + 1) & ~(size_t)1);
-    pl.lds_w = sizeof(float) * NLK_BM_WAVES * per_wave;
-    if (pl.lds_w > 160 * 1024) { pl.generic = true; pl.wide = false; }
-    pl.maxm_w = (ncand + 63) / 64;
-  }
+  if ((rc = nlk_match_plan(g, c->sw, &pl.mp))) return rc;
   // Packed lists (nlk_common.h): kept by the tiled matchers wherever k_group8m's packed instantiation could read them
   // (nlk_packed_geom; the matcher flags the targets whose record is valid, tu_group8.hip decides per launch).
   // NLK_PACKED_LISTS=0: none kept, the 32-bit lists only.
-  const bool packed = !pl.generic && nlk_or(c->sw.packed_lists, 1) != 0 && nlk_packed_geom(g);
+  const bool packed = !pl.mp.generic && nlk_or(c->sw.packed_lists, 1) != 0 && nlk_packed_geom(g);
   c->last = {g, pl.img_match, pl.img_cur, pl.img_prev, pl.img_diff, true, packed};
   return NLK_OK;
 }
@@ -366,19 +285,8 @@ static int match_rows(nlk_ctx* c, const NlkPlan& pl, hipStream_t stream, int r0,
                       uint64_t* marks_ext = nullptr) {
   const NlkGeom gb = band_geom(pl.g, r0, rows);
   const NlkRecView v = view_rows(c, pl.g, stream, r0, band, marks_ext);
-  if (pl.generic) return nlk_launch_match_generic(c, v, gb, pl.img_match);
-  NlkTile tl = pl.tl;
-  tl.nty = (rows + tl.tgy - 1) / tl.tgy;
-  if (pl.wide && !(pl.wide0_zeroed && r0 == 0 && band == 0))
-    HIPCHK(c, hipMemsetAsync(v.wide, 0, sizeof(uint32_t), stream));
-  int rc = nlk_launch_match(c, v, gb, tl, pl.lds, pl.img_match, pl.maxm, false);
-  if (rc) return rc;
-  if (pl.wide) {
-    NlkTile tw = pl.tw;
-    tw.nty = tl.nty;
-    rc = nlk_launch_match(c, v, gb, tw, pl.lds_w, pl.img_match, pl.maxm_w, true);
-  }
-  return rc;
+  // (the wide queue's length is cleared here unless the layout kernel has done it)
+  return nlk_launch_match(c, v, gb, pl.mp, !(pl.wide0_zeroed && r0 == 0 && band == 0), pl.img_match);
 }
 
 // The mask replay inside the group kernel's launch (k_group8m.h, NlkGTile::chase): the replay of a grid is a chain

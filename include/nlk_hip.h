@@ -698,6 +698,22 @@ int nlk_host_tables(int psz, float *basis, float *window, float *basis12_regs);
  * that byte; either may be NULL. NLK_EINVAL where the target cannot have a valid record (more than 32 candidates, r
  * above 7, pass-through) or the displacement lies outside the radius. */
 int nlk_host_packed_entry(int px, int py, int dx, int dy, int r, int k, int passthrough, unsigned int *byte, int *back);
+/* The launch plan of a frame call's block matching (csrc/tu_match.hip: nlk_match_plan), through the geometry code and
+ * the planner the frame calls run (tests only; no context, no device). w x h x ch, the parameters, smoother and
+ * have_prev as a frame call takes them; rows = target rows of the call (a strip, a band), 0 = the whole grid. The
+ * NLK_* switches are read from the environment at the call. out[]:
+ *    0 generic   the generic kernel runs instead of the tiled ones (the fields below are then not used by a launch)
+ *    1 wide      a second launch takes the queued targets that search the wider spatial window
+ *    2.. the dominant tile: 2 tgx, 3 tgy (targets per tile), 4 bx (targets per block along x), 5 threads per
+ *        workgroup, 6 block (blocks share their squared differences), 7 order (1 = block-summed), 8 halo, 9 rwp (LDS
+ *        row stride, floats), 10 rh_max (LDS rows), 11 ksel_max (list capacity), 12 ntx (tiles along x),
+ *        13 rounds class (2, 7 or 16 rounds of 64 candidates: the kernel instantiation), 14 dynamic LDS bytes
+ *   15.. the wide tile (all 0 without one): 15 halo, 16 rwp, 17 rh_max, 18 rounds class, 19 dynamic LDS bytes
+ * Returns what the frame call returns for inputs it refuses (NLK_EUNSUP: patch size; NLK_EINVAL: image smaller than a
+ * patch, rows outside the grid, negative radii) and then writes nothing. */
+#define NLK_MATCH_PLAN_FIELDS 20
+int nlk_host_match_plan(int w, int h, int ch, const struct nlkalman_params *prms, int smoother, int have_prev, int rows,
+                        int out[NLK_MATCH_PLAN_FIELDS]);
 /* how many targets of the context's last match phase carry a valid packed record (tests only; synchronises) */
 int nlk_ctx_count_packed(nlk_ctx *ctx, int *count);
 

@@ -191,7 +191,7 @@ def test_smoother_sigma50_full_size_1080p(ctx, built, O, synth):
 # ---------------------------------------------------------------- 4. the matcher's plans under long lists
 
 def _plan(psz, ch, sx, st, k, ntagg, have_prev, smoother, tgx, tgy, block):
-    """The matcher's choice for a tiled shape (nlk_hip.hip: plan_frame; tu_match.hip: nlk_launch_match_generic):
+    """The matcher's choice for a tiled shape (tu_match.hip: nlk_match_plan and the generic launcher, restated):
     ('tile', wavefronts, bytes), ('generic', None, bytes) or ('refused', None, bytes); and the wide queue's bytes
     (FLT1 temporal with sx > st) or None."""
     step = psz // 2
@@ -274,7 +274,7 @@ def test_wide_queue_with_long_lists(ctx, built, O):
 
 def test_generic_matcher_refuses_above_its_lds(ctx, built, O):
     """Capacities whose lists do not fit k_bm_generic's LDS: an NlkError that names it, with the byte count of the
-    formula (tu_match.hip: nlk_launch_match_generic)."""
+    formula (tu_match.hip: launch_match_generic)."""
     psz, ch, sx, st, n = 8, 3, 10, 5, 11000
     w, h, sigma = 24, 24, 20.0
     (kind, _, lds), _ = _plan(psz, ch, sx, st, n, n, False, False, 4, 2, False)
