@@ -30,7 +30,7 @@ HIP_SYMBOLS = [
     "nlk_dev_strip_match", "nlk_dev_strip_match_rows", "nlk_dev_mask_commit", "nlk_dev_strip_group",
     "nlk_tvl1_default_params", "nlk_tvl1_scales", "nlk_dev_tvl1_flow", "nlk_dev_gray",
     "nlk_dev_occlusion_mask", "nlk_dev_image_dct", "nlk_dev_copy_block", "nlk_host_tables", "nlk_ctx_set_deterministic", "nlk_dev_zero", "nlk_dev_add", "nlk_dev_copy_peer",
-    "nlk_filter_frame_host", "nlk_smooth_frame_host", "nlk_dev_strip_match_part", "nlk_ctx_reload_switches", "nlk_ctx_last_group_shape", "nlk_ctx_last_group_packed", "nlk_host_packed_entry", "nlk_host_match_plan", "nlk_ctx_count_packed", "nlk_ctx_set_strip_accumulator",
+    "nlk_filter_frame_host", "nlk_smooth_frame_host", "nlk_dev_strip_match_part", "nlk_ctx_reload_switches", "nlk_ctx_last_group_shape", "nlk_ctx_last_group_packed", "nlk_host_packed_entry", "nlk_host_match_plan", "nlk_host_tvl1_plan", "nlk_ctx_count_packed", "nlk_ctx_set_strip_accumulator",
     "nlk_strips_create", "nlk_strips_destroy", "nlk_strips_last_error", "nlk_rccl_unique_id", "nlk_strips_rccl_init",
     "nlk_strips_transport", "nlk_strips_load", "nlk_strips_set_options", "nlk_strips_step", "nlk_strips_sync",
     "nlk_strips_own_rows", "nlk_strips_ctx", "nlk_strips_geometry", "nlk_strips_stats", "nlk_strips_set_dry_run",
@@ -262,6 +262,7 @@ def hip():
         L.nlk_ctx_last_group_packed.argtypes = [vp]
         L.nlk_host_packed_entry.argtypes = [i, i, i, i, i, i, i, C.POINTER(C.c_uint), C.POINTER(i)]
         L.nlk_host_match_plan.argtypes = [i, i, i, C.POINTER(Params), i, i, i, C.POINTER(i)]
+        L.nlk_host_tvl1_plan.argtypes = [i, i, C.POINTER(Tvl1Params), i, C.POINTER(i), C.POINTER(i)]
         L.nlk_ctx_count_packed.argtypes = [vp, C.POINTER(i)]
         L.nlk_ctx_set_strip_accumulator.argtypes = [vp, vp]
         L.nlk_strips_create.argtypes = [C.POINTER(vp), i, C.POINTER(i), i, i, i, i, i, C.c_float, C.POINTER(Params), i, i]
@@ -522,6 +523,22 @@ def host_match_plan(w, h, ch, params, smoother=False, have_prev=False, rows=0):
     if rc:
         raise NlkError(hip().nlk_last_error(None).decode(), rc)
     return dict(zip(MATCH_PLAN_FIELDS, out))
+
+
+TVL1_PLAN_FIELDS = ("nx", "ny", "solved", "driver", "threads", "shape", "tw", "th", "gx", "gy", "inline", "look")
+TVL1_DRIVER_WG, TVL1_DRIVER_BLOCKED, TVL1_DRIVER_PLAIN = 0, 1, 2
+
+
+def host_tvl1_plan(w, h, params):
+    """The plan of every pyramid level of a TV-L1 flow call, finest first, as a list of dicts of TVL1_PLAN_FIELDS
+    (nlk_host_tvl1_plan: the flow call's checks, layout walk and level planner, the NLK_TV_* switches from the
+    environment; no device needed). NlkError, whose args[1] is the flow call's error code, for refused inputs."""
+    n, levels = len(TVL1_PLAN_FIELDS), C.c_int(0)
+    out = (C.c_int * (64 * n))()
+    rc = hip().nlk_host_tvl1_plan(int(w), int(h), C.byref(params), 64, out, C.byref(levels))
+    if rc:
+        raise NlkError(hip().nlk_last_error(None).decode(), rc)
+    return [dict(zip(TVL1_PLAN_FIELDS, out[s * n:(s + 1) * n])) for s in range(levels.value)]
 
 
 def reload_switches():

@@ -235,14 +235,16 @@ __global__ void k_tv_zoom(const float* __restrict__ in_a, float* __restrict__ ou
 // flow update; forward gradient + dual update} until the mean squared update drops below
 // epsilon^2. The per-pixel steps are the device functions below (the reference's arithmetic,
 // type for type; u and p are updated in place: each step writes only what it read at the own
-// pixel). Two drivers use them:
-//  * the smallest levels (up to NLK_TV_WG_PIXELS pixels) run ENTIRELY inside one 1024-thread workgroup
+// pixel). Three drivers use them (tu_tvl1.hip: nlk_tv_plan says which one a level gets):
+//  * the smallest levels (up to NLK_TV_WG_PIXELS pixels) run ENTIRELY inside one workgroup of up to 1024 threads
 //    (k_tv_level_wg): all warps and iterations, phases separated by workgroup barriers, the stop
 //    test evaluated in the kernel. An iteration costs ~1 us there instead of two launches of
 //    ~5 us each, and nothing is read back;
-//  * larger levels launch one kernel per half iteration (k_tv_primal / k_tv_dual); the stop test
-//    also lives on the device (iterations after the converged one return at once) and the host
-//    looks at the state only between batches of iterations.
+//  * larger levels run NLK_TV_K iterations per launch on tiles held in LDS (k_tv_block, below: the blocked
+//    driver); the stop test lives on the device (batches after the converged one return at once) and the
+//    host looks at the state only between groups of batches;
+//  * the plain recursion launches one kernel per half iteration (k_tv_primal / k_tv_dual) with the same
+//    device-side stop test: NLK_TV_UNBLOCKED, kept as the blocked driver's oracle.
 // (A single persistent kernel with grid-wide barriers was measured too: on this multi-XCD part a
 // device-scope release/acquire per phase costs ~10 us, more than the launches it replaces.)
 struct NlkTvLevel {
@@ -571,12 +573,11 @@ __global__ void __launch_bounds__(256) k_tv_dual(NlkTvLevel L, int n, int nparts
 //               so that all take the same decision without a kernel in between): it finds the
 //               first iteration that satisfies the stop test; later batches are no-ops, and if
 //               the batch ran past the stop, that batch is redone from its input with fewer
-//               iterations by the launch that closes a group of batches (mode 1), which also
+//               iterations by the launch that closes a group of batches (NLK_TV_MODE_CLOSE), which also
 //               judges the group's last batch. A launch never reads a state field it writes
 //               (workgroups of one launch do not run together), except `stop_iter`, where both
 //               values lead to the same action.
-#define NLK_TV_K 4   // iterations per launch where the grid fills the chip (halo work grows with K),
-#define NLK_TV_K2 8  // and on the small levels, whose launches are latency-bound
+#define NLK_TV_K 4   // iterations per launch (halo work grows with K)
 #define NLK_TV_TW 64
 #define NLK_TV_TH 16   // tile rows: 16 (region 72 x 24: 2 pixel slots per thread for 1 tile pixel) or, for levels
 #define NLK_TV_TH2 32  // with enough tiles to fill the chip, 32 (72 x 40: 3 slots for 2 tile pixels)
@@ -633,9 +634,10 @@ __device__ __forceinline__ void nlk_tv_post(const NlkTvLevel& L, unsigned seq) {
   __hip_atomic_store(&m->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// mode 0: a batch; 2: a batch that first judges the previous one; 1: closes a group of batches
-// (n0, count = the group's last batch, judged here; in / out = the buffers of the warp's FIRST
-// batch); 3: closes a group whose batches were all judged by k_tv_decide.
+// what a launch of k_tv_block is (its `mode` argument): a batch; the launch that closes a group of batches (n0, count =
+// the group's last batch, judged here; in / out = the buffers of the warp's FIRST batch); a batch that first judges the
+// previous one; the launch that closes a group whose batches were all judged by k_tv_decide.
+enum NlkTvMode { NLK_TV_MODE_BATCH = 0, NLK_TV_MODE_CLOSE = 1, NLK_TV_MODE_JUDGE_BATCH = 2, NLK_TV_MODE_CLOSE_DECIDED = 3 };
 // Judging inside the batches saves a launch per batch where the grid is small (every workgroup
 // re-adds all partial sums: cheap for a few hundred workgroups, not for thousands)
 template <int TW, int TH, int BT, int KI>
@@ -646,14 +648,14 @@ k_tv_block(NlkTvLevel L, NlkTvBuf in, NlkTvBuf out, int n0, int count, int mode,
   __shared__ double red[KI][4];
   __shared__ float errs[KI];
   const int nblocks = gridDim.x * gridDim.y, block = blockIdx.y * gridDim.x + blockIdx.x;
-  if (mode == 1 || mode == 3) {
+  if (mode == NLK_TV_MODE_CLOSE || mode == NLK_TV_MODE_CLOSE_DECIDED) {
     const bool poster = block == 0 && threadIdx.x == 0;
     if (L.st->stop_iter < NLK_TV_MAXIT) {  // found by a batch of this group
       if (poster) nlk_tv_post(L, seq);
       if (L.st->redo == 0) return;
       n0 = L.st->redo_n0;
       count = L.st->redo;
-    } else if (mode == 3) {
+    } else if (mode == NLK_TV_MODE_CLOSE_DECIDED) {
       if (poster) nlk_tv_post(L, seq);
       return;
     } else {
@@ -674,7 +676,7 @@ k_tv_block(NlkTvLevel L, NlkTvBuf in, NlkTvBuf out, int n0, int count, int mode,
     if ((n0 / KI) & 1) { const NlkTvBuf t = in; in = out; out = t; }
   } else {
     if (n0 >= L.st->stop_iter) return;
-    if (mode == 2) {
+    if (mode == NLK_TV_MODE_JUDGE_BATCH) {
       const int n0p = n0 - KI;
       bool stop;
       float err;

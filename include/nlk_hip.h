@@ -714,6 +714,24 @@ int nlk_host_packed_entry(int px, int py, int dx, int dy, int r, int k, int pass
 #define NLK_MATCH_PLAN_FIELDS 20
 int nlk_host_match_plan(int w, int h, int ch, const struct nlkalman_params *prms, int smoother, int have_prev, int rows,
                         int out[NLK_MATCH_PLAN_FIELDS]);
+/* The plan of every pyramid level of a TV-L1 flow call (csrc/tu_tvl1.hip: nlk_tv_plan), through the parameter check and
+ * the scratch layout walk nlk_dev_tvl1_flow runs (tests only; no context, no device). The NLK_TV_* switches are read from
+ * the environment at the call. out[] receives one row of NLK_TVL1_PLAN_FIELDS ints per level, finest first, and
+ * *nlevels their number (prms->nscales); max_levels = the rows out[] has room for. A row:
+ *    0 nx, 1 ny   the level's size
+ *    2 solved     the level is at or above prms->fscale (finer levels only receive the upsampled flow; their rows show
+ *                 the plan they would get)
+ *    3 driver     0 one workgroup solves the level, 1 the blocked driver, 2 the plain recursion (NLK_TV_UNBLOCKED)
+ *    4 threads    of the one workgroup, or of a blocked batch's workgroups
+ *    5 shape, 6 tw, 7 th   blocked: the tile shape's number (0, 1, 2 or 4), tile width and height
+ *    8 gx, 9 gy   the grid: of the blocked batches, or of the plain recursion's 64 x 4 pixel workgroups
+ *   10 inline     blocked: a batch judges its predecessor's stop test itself (0: a k_tv_decide launch between batches)
+ *   11 look       blocked: batches between two looks at the solver state
+ * A field that does not apply to the level's driver is 0. Returns what nlk_dev_tvl1_flow returns, with its messages, for
+ * sizes and parameters it refuses, NLK_EINVAL for a NULL pointer or max_levels below the level count, and then writes
+ * nothing. */
+#define NLK_TVL1_PLAN_FIELDS 12
+int nlk_host_tvl1_plan(int w, int h, const struct nlk_tvl1_params *prms, int max_levels, int *out, int *nlevels);
 /* how many targets of the context's last match phase carry a valid packed record (tests only; synchronises) */
 int nlk_ctx_count_packed(nlk_ctx *ctx, int *count);
 

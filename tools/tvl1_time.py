@@ -18,14 +18,13 @@ ctx.gray(g0, d0, w, h, 3); ctx.gray(g1, d1, w, h, 3)
 d_f = ctx.alloc(w * h * 8)
 p = pkg.tvl1_params(w, h, lam=lam, fscale=fscale)
 it = ctx.tvl1_flow(d_f, g0, g1, w, h, p); ctx.sync()
-for batch in (os.environ.get("NLK_TV_BATCH", "12"),):
-    t0 = time.perf_counter()
-    reps = 3
-    for _ in range(reps):
-        it = ctx.tvl1_flow(d_f, g0, g1, w, h, p)
-    ctx.sync()
-    dt = (time.perf_counter() - t0) / reps
-    print(f"{w}x{h} fscale {fscale} lambda {lam}: {p.nscales} scales, {it} iterations, {dt*1e3:.2f} ms "
-          f"({dt/it*1e6:.1f} us per iteration, {w*h/dt/1e6:.1f} Mpix/s)")
+t0 = time.perf_counter()
+reps = 3
+for _ in range(reps):
+    it = ctx.tvl1_flow(d_f, g0, g1, w, h, p)
+ctx.sync()
+dt = (time.perf_counter() - t0) / reps
+print(f"{w}x{h} fscale {fscale} lambda {lam}: {p.nscales} scales, {it} iterations, {dt*1e3:.2f} ms "
+      f"({dt/it*1e6:.1f} us per iteration, {w*h/dt/1e6:.1f} Mpix/s)")
 f = ctx.download(d_f, (h, w, 2))
 print("flow median", np.median(f[..., 0]), np.median(f[..., 1]), "finite", np.isfinite(f).all())
