@@ -230,9 +230,15 @@ static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* pr
   int rc = check_frame(c, cur, cur, w, h, ch, P);
   if (rc) return rc;
   NLK_USE_DEVICE(c);
-  nlk_set_lazy_active(c, 0, 0, nullptr);  // (whatever replays this call's mask: `active` holds its bytes unless set again)
   NlkGeom& g = pl.g;
   if ((rc = nlk_frame_geom(c, g, w, h, ch, sigma, P, oy, ngy, smoother, prev != nullptr, basic != nullptr))) return rc;
+  // The argument checks are passed: from here on the call touches the context (scratch that regrows, planar images,
+  // queue counters, then the records), so what the call before left for nlk_dev_strip_group and
+  // nlk_ctx_read_records is gone - its decisions too, which may still be tagged words awaiting nlk_ctx_flush_active.
+  // (Not before: a call refused above leaves all of it in place.) The state is valid again once this call's match
+  // phase has been enqueued (match_done); a call refused in between leaves the context without one.
+  c->last.valid = false;
+  nlk_set_lazy_active(c, 0, 0, nullptr);  // (whatever replays this call's mask: `active` holds its bytes unless set again)
   const int ngrid = g.ngx * g.ngy;
   const int npix = w * h;
 
@@ -275,9 +281,13 @@ static int plan_frame(nlk_ctx* c, NlkPlan& pl, const float* cur, const float* pr
   // (nlk_packed_geom; the matcher flags the targets whose record is valid, tu_group8.hip decides per launch).
   // NLK_PACKED_LISTS=0: none kept, the 32-bit lists only.
   const bool packed = !pl.mp.generic && nlk_or(c->sw.packed_lists, 1) != 0 && nlk_packed_geom(g);
-  c->last = {g, pl.img_match, pl.img_cur, pl.img_prev, pl.img_diff, true, packed};
+  c->last = {g, pl.img_match, pl.img_cur, pl.img_prev, pl.img_diff, false, packed};  // (valid: match_done)
   return NLK_OK;
 }
+
+// the match phase of the plan is enqueued (all of it, or the part this call was asked for): the context again holds
+// what nlk_dev_strip_group, nlk_dev_strip_commit_group and nlk_ctx_read_records work on
+static inline void match_done(nlk_ctx* c) { c->last.valid = true; }
 
 // phase 1 for the target rows [r0, r0 + rows) of the plan: block matching + selection on `stream`;
 // leaves topk / gcoords / tinfo of those rows in the context's buffers, and their mark words there or in `marks_ext`
@@ -377,6 +387,7 @@ static int frame_accumulate(nlk_ctx* c, float* acc, const float* cur, const floa
   uint8_t* active = (uint8_t*)c->active.p;
   if (nb == 1) {
     if ((rc = match_rows(c, pl, c->stream, 0, g.ngy, 0))) return rc;
+    match_done(c);
     mark(c, 2);
     if (chase)  // (the bytes of `active` only when somebody reads the records)
       return chase_group(c, acc, (const uint64_t*)c->marks.p, active, g.ngx, 0, g.ngy, g.R, nullptr);
@@ -397,6 +408,7 @@ static int frame_accumulate(nlk_ctx* c, float* acc, const float* cur, const floa
   for (int b = 0; b <= nb; ++b) r0[b] = (int)((long)g.ngy * b / nb);
   for (int b = 0; b < nb; ++b)
     if ((rc = match_rows(c, pl, st[b & 1], r0[b], r0[b + 1] - r0[b], b))) return rc;
+  match_done(c);
   for (int b = 0; b < nb; ++b)
     if ((rc = band_step(c, st[b & 1], acc, r0[b], r0[b + 1], b, b > 0 ? ev[1 + ((b - 1) & 1)] : nullptr, ev[1 + (b & 1)]))) return rc;
   HIPCHK(c, hipEventRecord(ev[3], st[1]));
@@ -422,6 +434,13 @@ int nlk_dev_strip_match_part(nlk_ctx* c, const float* cur, const float* prev, co
                              void* marks_out, int* reach) {
   if (lay0 < 0 || lay1 > h || lay0 > lay1 || v0 < 0 || v1 > h || v0 > v1)
     return fail(c, NLK_EINVAL, "layout rows [%d, %d) / validity rows [%d, %d) outside the %d-row strip", lay0, lay1, v0, v1, h);
+  // (every check that can refuse the call on its arguments runs before plan_frame touches the context)
+  if (ngy >= 1 && (r0 < 0 || rows < 0 || r0 + rows > ngy))
+    return fail(c, NLK_EINVAL, "rows [%d, %d) outside the strip's %d target rows", r0, r0 + rows, ngy);
+  struct nlk_frame_grid fg;
+  if (marks_out && P && w > 0 && h > 0 && nlk_frame_grid(w, h, P, smoother, prev != nullptr, &fg) == NLK_OK && fg.reach > 3)
+    return fail(c, NLK_EUNSUP, "group reach %d grid cells > 3: 64-bit mark words cannot describe it (row strips "
+                "across GPUs are limited to reach 3; whole-frame calls are not)", fg.reach);
   NlkPlan pl;
   int rc = plan_frame(c, pl, cur, prev, basic, w, h, ch, sigma, P, oy, ngy, smoother, 1, nullptr, false);
   if (rc) return rc;
@@ -429,12 +448,9 @@ int nlk_dev_strip_match_part(nlk_ctx* c, const float* cur, const float* prev, co
   if ((rc = layout_rows(c, c->stream, cur, prev, basic, c->strip_acc, pl.img_diff, w, h, ch, pl.g.psz, lay0, lay1, v0, v1)))
     return rc;
   mark(c, 1);
-  if (r0 < 0 || rows < 0 || r0 + rows > pl.g.ngy) return fail(c, NLK_EINVAL, "rows [%d, %d) outside the strip's %d target rows", r0, r0 + rows, pl.g.ngy);
-  if (marks_out && pl.g.R > 3)
-    return fail(c, NLK_EUNSUP, "group reach %d grid cells > 3: 64-bit mark words cannot describe it (row strips "
-                "across GPUs are limited to reach 3; whole-frame calls are not)", pl.g.R);
   // the matcher writes the mark words of these rows straight to their place in the caller's array
   if (rows > 0 && (rc = match_rows(c, pl, c->stream, r0, rows, 0, (uint64_t*)marks_out))) return rc;
+  match_done(c);
   mark(c, 2);
   if (reach) *reach = pl.g.R;
   return NLK_OK;
@@ -638,6 +654,7 @@ static int frame_host(nlk_ctx* c, float* out_h, const float* cur_h, const float*
     HIPCHK(c, hipEventRecord(c->band_ev[E_DONE][b], s));
     up0 = up1; v0 = v1; nz0 = nz[b + 1];
   }
+  match_done(c);
   if (trace) clock_gettime(CLOCK_MONOTONIC, &ts1);
   // the rows go back band by band: every upload has been issued by now, the kernels of the first bands are done
   for (int b = 0; b < nb; ++b) {

@@ -119,6 +119,17 @@ int nlk_ctx_last_group_packed(nlk_ctx *ctx);
  * default stream itself (what torch.cuda.current_stream() is unless changed), so
  * that the kernels order with the caller's own work on that stream.
  * nlk_ctx_use_own_stream switches back to the context's private stream. */
+/* Every entry point puts ALL its launches, memsets and copies on that stream, or behind it: a call that also uses
+ * the context's second stream (frames worked in bands, NLK_BANDS) starts that stream behind the work already on the
+ * caller's and joins it back before it returns, so the caller's stream alone orders the call with the work before and
+ * after it (tests/test_stream_order.py holds every entry point to this).
+ * Which calls wait for the device. The nlk_dev_* entry points only enqueue, with these exceptions: nlk_dev_tvl1_flow
+ * reads its solver state back while it runs and returns with the flow complete; a frame or strip call waits once when
+ * it meets a patch size other than the last one's (it uploads the DCT and window tables), nlk_dev_nlf_forward /
+ * _inverse once per new table; any call may wait when a scratch buffer of the context has to grow (the old one is
+ * freed). A context that has run a call of the same sizes and parameters before runs it again without waiting.
+ * nlk_h2d, nlk_d2h, nlk_sync, nlk_dev_free, nlk_ctx_read_records, nlk_ctx_flush_active, nlk_ctx_count_packed,
+ * nlk_ctx_get_timings and the host-pointer frame calls wait by definition. */
 int nlk_ctx_set_stream(nlk_ctx *ctx, void *hip_stream);
 int nlk_ctx_use_own_stream(nlk_ctx *ctx);
 void *nlk_ctx_get_stream(nlk_ctx *ctx);
@@ -567,7 +578,19 @@ int nlk_dev_frame_normalize(nlk_ctx *ctx, float *out, const float *acc,
  * of the WHOLE patch grid, and `strip_group` processes the strip's targets with
  * its slice of the resulting active flags. `marks_out` / `active` are device
  * buffers of ngx*ngy uint64 / bytes; `reach` receives the R to hand to
- * mask_commit. strip_group uses the state strip_match left in the context. */
+ * mask_commit. strip_group (and strip_commit_group) use the state the context's LAST accepted match phase left in it:
+ * geometry, planar images and lists of the last nlk_dev_strip_match* call - or of a whole-frame or
+ * nlk_dev_frame_accumulate call made since, whose match phase replaces that state like a strip_match over its
+ * whole grid would (a strip_group after a whole-frame call is that frame's group phase, acc being a whole-frame
+ * accumulator and `active` its ngx * ngy decisions).
+ * Refused calls. A frame or strip call refused by its argument checks, before anything is enqueued - a NULL image or
+ * parameters, a size below 1, a patch size the kernels do not cover, an image smaller than a patch, target rows that
+ * leave the strip, negative radii; for nlk_dev_strip_match*: rows outside the strip's target rows, layout rows outside
+ * the strip, a reach above 3 with mark words asked for - leaves that state, and the records of nlk_ctx_read_records,
+ * as they were. A call that fails later (a HIP error, an allocation that fails, a matcher that needs more LDS than a
+ * workgroup has) has already overwritten part of them: it leaves the context WITHOUT a match state, and
+ * nlk_dev_strip_group, nlk_dev_strip_commit_group, nlk_ctx_read_records and nlk_ctx_count_packed return NLK_EINVAL
+ * until a frame or strip call has been accepted again. */
 int nlk_dev_strip_match(nlk_ctx *ctx, const float *cur, const float *prev,
                         const float *basic, int w, int h, int ch, float sigma,
                         const struct nlkalman_params *prms, int oy, int ngy,
@@ -610,7 +633,9 @@ int nlk_dev_strip_commit_group(nlk_ctx *ctx, float *acc, const void *marks, int 
  * for a strip - and wait. No-op otherwise. */
 int nlk_ctx_flush_active(nlk_ctx *ctx);
 
-/* per-target records of the last frame call, copied to host (tests only):
+/* per-target records of the last frame or strip call that ran a match phase (refused calls: see
+ * nlk_dev_strip_match; a whole-frame call on an image smaller than a patch has no targets, runs no match phase and
+ * leaves the records of the call before it), copied to host (tests only):
  * active[ngrid] (1 = processed), nsel/np0/nagg[ngrid], topk[ngrid*kmax] and
  * gcoords[ngrid*gmax] packed as x | y << 16. Any pointer may be NULL. */
 int nlk_ctx_read_records(nlk_ctx *ctx, int *ngrid, int *kmax, int *gmax,

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import cases
+from ctx_ops import check_records as _check_records   # (shared with tests/test_context_history.py)
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -33,22 +34,6 @@ def _dev_frame(ctx, smoother, cur, prev, basic, sigma, p):
         if x:
             ctx.free(x)
     return out, rec
-
-
-def _check_records(rec, tr, what):
-    act_o, act_g = tr["active"].astype(bool), rec["active"].astype(bool)
-    assert np.array_equal(act_o, act_g), f"{what}: processed-mask decisions differ"
-    a = act_o
-    for f in ("nsel", "np0", "nagg"):
-        assert np.array_equal(tr[f][a], rec[f][a]), f"{what}: {f} differs"
-    k = tr["topk"].shape[1]
-    col = np.arange(k)[None, :]
-    live = a[:, None] & (col < tr["nsel"][:, None])
-    assert np.array_equal(tr["topk"][live], rec["topk"][:, :k].astype(np.int64)[live]), f"{what}: k-NN lists differ"
-    g = tr["gcoords"].shape[1]
-    col = np.arange(g)[None, :]
-    live = a[:, None] & (col < tr["nagg"][:, None])
-    assert np.array_equal(tr["gcoords"][live], rec["gcoords"][:, :g].astype(np.int64)[live]), f"{what}: group members differ"
 
 
 @pytest.mark.parametrize("name", list(cases.CASES))
